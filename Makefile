@@ -80,7 +80,7 @@ tests/cpp/test_host: tests/cpp/test_host.cpp $(HOST_LIB)
 tests/cpp/test_bls_host: tests/cpp/test_bls_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
-# per-request path benchmark (bench.py runs it): threads calling verify() / verifySig()
+# per-request path benchmark (bench.py --full runs it): threads calling verify() / verifySig()
 tools/host_bench: tools/host_bench.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall -DCONCORD_BFT_TESTING $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../concord-bft_amd'
 

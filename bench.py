@@ -1,8 +1,18 @@
 #!/usr/bin/env python3
 """Headline benchmark: Ed25519 batch verification on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run does what the headline figure needs and no more: it generates the batches, loads the
+key tables, runs the headline pipeline untimed until the GPU is warm, then W warm-up steps and the
+K timed steps, and prints the contract's line (`value`, `ms_per_step`).  `--dump-outputs DIR` also
+writes the verdicts of the last timed step to DIR/verdicts.npy (float32, one 0/1 per signature).
+Everything else described below -- the parity gate, the check of every step against OpenSSL, the
+PCIe-inclusive and cold-start rates, config #5, the step spread and clocks, the comb-radix cliff,
+the roofline, the CPU baseline, the latencies and the config #3 / #4 / RSA side measurements -- is
+measured only with `--full`, which times the same headline region on a GPU warmed by those other
+legs and prints the long line.
 
 `python bench.py --gpus N` with N > 1 and no launcher starts the N ranks itself (a child
 torch.distributed.run, before anything touches the GPU) and exits with its code; a rank whose
@@ -67,6 +77,9 @@ OPS_ENCODE = 254 * 44 + 13 * 72            # R' inversion + encode
 SHA_OPS_PER_BLOCK = 5000
 # PCIe Gen5 x16 host -> device: 32 GT/s x 16 lanes x 128/130 = 63.0 GB/s per direction
 PCIE_PEAK = 32e9 * 16 * 128 / 130 / 8
+# A plain run's untimed steps before the warm-up: the first ~200 batches after idle run 10-20 % slow
+# (the ramp of DESIGN.md §12.3), and `value` is the rate of a warm GPU; 400 steps are ~50 ms.
+SETTLE_STEPS = 400
 
 
 def ops_per_verify(m: int) -> int:
@@ -78,6 +91,12 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every other leg (parity gate, per-step OpenSSL checks, PCIe-inclusive and "
+                         "cold-start rates, config #3 / #4 / #5, RSA, roofline, CPU baseline, latencies) and print "
+                         "the long line; without it only the headline is set up, warmed, timed and printed")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the verdicts of the last timed step to DIR/verdicts.npy (float32, 1 = accept)")
     ap.add_argument("--batch", type=int, default=65536)
     ap.add_argument("--msg-len", type=int, default=256)
     ap.add_argument("--distinct", type=int, default=8,
@@ -179,8 +198,9 @@ def main():
     numa = _bind_near_gpu(torch, dev.index) if world > 1 else None
     cores, quota = _cpu_cores()
     cpu_threads = args.cpu_threads or cores
-    clocks = gpu_clocks.Clocks(torch, dev.index)
-    clk_before = clocks.read()  # here, not between the warm-up and the timed region (no idle gap there)
+    full = args.full  # every leg beside the headline; a plain run skips them (and their expectations)
+    clocks = gpu_clocks.Clocks(torch, dev.index) if full else None
+    clk_before = clocks.read() if full else None  # here, not between the warm-up and the timed region (no idle gap there)
 
     # ---- workload: this rank's static shard (weak scaling).  --distinct batches (default 8), each its
     # own set of n OpenSSL-signed L-byte messages over the same 4,096 keys with --invalid-frac
@@ -194,17 +214,20 @@ def main():
     nwords = (n + 63) // 64
     gen_t0 = time.perf_counter()
     sets = [workload.make_sigset(n, nkeys=args.nkeys, msg_len=L, seed=0xC0FFEE + rank + 7919 * b,
-                                 invalid_frac=args.invalid_frac, threads=min(cpu_threads, 64)) for b in range(nb)]
+                                 invalid_frac=args.invalid_frac, threads=min(cpu_threads, 64),
+                                 compute_expected=full) for b in range(nb)]  # the same batches with or without --full
     gen_s = time.perf_counter() - gen_t0
     ss = sets[0]
-    invalid = [int((~s.expected).sum()) for s in sets]
+    invalid = [int((~s.expected).sum()) for s in sets] if full else None
     ctx = cb.Context(device=dev.index, max_batch=n)
-    # parity first: every golden verdict class (Ed25519 edge cases through both key modes, the
-    # RELIC key fixture, RSA accepts and rejects); any mismatch exits non-zero before timing
-    parity = parity_gate.run(ctx, rsa=args.extras, relic=args.extras)
-    # the OpenSSL verdict words of every batch on this device (and, N > 1, every rank's)
-    exp_rows = torch.from_numpy(np.stack([mg.bools_to_words(s.expected) for s in sets])).to(dev)
-    all_exp = mg.all_gather_rows(exp_rows, world, dist) if world > 1 else None
+    parity = exp_rows = all_exp = None
+    if full:
+        # parity first: every golden verdict class (Ed25519 edge cases through both key modes, the
+        # RELIC key fixture, RSA accepts and rejects); any mismatch exits non-zero before timing
+        parity = parity_gate.run(ctx, rsa=args.extras, relic=args.extras)
+        # the OpenSSL verdict words of every batch on this device (and, N > 1, every rank's)
+        exp_rows = torch.from_numpy(np.stack([mg.bools_to_words(s.expected) for s in sets])).to(dev)
+        all_exp = mg.all_gather_rows(exp_rows, world, dist) if world > 1 else None
     gstream = torch.cuda.Stream(device=dev) if world > 1 else None
 
     def verdicts(steps):  # per-step verdict words (+ their all-gathers when N > 1)
@@ -229,7 +252,7 @@ def main():
     # the batches as a caller builds them: each in one pinned host block (cbft_host_alloc) laid out as
     # cbft_ed25519_batch_layout says, so each step's host -> device transfer is one DMA
     blocks = []
-    for s in sets:
+    for s in sets if full else ():  # the PCIe-inclusive leg's inputs
         blk, h_kidx, h_sig, b_raw = ctx.batch_views(n, L)
         h_kidx[:] = s.key_idx
         h_sig[:] = s.sig
@@ -292,17 +315,51 @@ def main():
         return go
 
     def headline():
-        """warm-up + the contract's timed region; every step's words checked after it."""
+        """warm-up + the contract's timed region; with --full every step's words are checked after
+        it.  Returns the time, the clocks and the region's verdict words."""
         drun_with(verdicts(max(args.warmup, 2)))(max(args.warmup, 2))
         ver = verdicts(args.steps)
         el = timed(drun_with(ver), args.steps)
-        clk = clocks.read()
-        require_exact(ver, "headline (device-resident)")
-        return el, clk
+        clk = clocks.read() if full else None
+        if full:
+            require_exact(ver, "headline (device-resident)")
+        return el, clk, ver
 
     t_keys = time.perf_counter()
     tid = ctx.load_keys(ss.pk, radix=args.comb_radix)  # key tables resident, like SigManager's verifiers
     key_load_ms = (time.perf_counter() - t_keys) * 1e3
+    if not full:
+        # ---- a plain run: the headline alone.  The GPU is warmed by SETTLE_STEPS untimed steps of
+        # the same pipeline (with --full the other legs do that), then the contract's W warm-up
+        # steps and K timed steps follow without a pause.
+        settle = SETTLE_STEPS
+        sver = verdicts(settle)
+        drun_with(sver)(settle)
+        elapsed, _, ver = headline()
+        dumped = _dump_outputs(args.dump_outputs, ver, args.steps, n, world) if (args.dump_outputs and rank == 0) else None
+        if rank == 0:
+            line = {
+                "metric": METRIC, "value": world * n * args.steps / elapsed, "unit": "verifies/s", "n_gpus": world,
+                "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
+                "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
+                "full": False,
+                "config": {"workload": "ed25519_verify_64k_256B_4096keys (BASELINE config #2, inputs resident in HBM: "
+                                       "sig + key index + msg, key tables resident)",
+                           "batch_per_gpu": n, "msg_len": L, "nkeys": args.nkeys, "comb_radix": args.comb_radix,
+                           "inputs": f"HBM (cbft_ed25519_verify_fixed_device, {nst} streams); verdict words stay in HBM",
+                           "timed_after": f"{settle} untimed steps of the same pipeline (warm GPU)",
+                           "batches": f"{nb} distinct signed batches per GPU cycled through the steps, "
+                                      f"{args.invalid_frac:.0%} planted invalid; verdicts are checked against "
+                                      f"OpenSSL only with --full",
+                           "parallelism": f"static shard x{world}"},
+                "outputs": dumped, "workload_gen_s": gen_s, "key_table_load_ms": key_load_ms,
+            }
+            print(json.dumps(line), flush=True)
+        del sver, ver
+        ctx.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # ---- the host pipeline's first check: one pass over every batch, before anything else is timed
     first = [np.zeros(nwords * 8, dtype=np.uint8) for _ in range(nb)]
     run(nb, first)
@@ -324,7 +381,7 @@ def main():
     # the same K steps right after the PCIe leg, whose PCIe-bound batches leave the GPU mostly idle:
     # the first ~200 device-resident batches after idle run 10-20 % slower (the memory-side clocks
     # ramp), so this is the cold-start figure, reported beside `value`
-    cold_elapsed, _ = headline()
+    cold_elapsed, _, _ = headline()
     parity["config2_headline"] = {"batches": nb, "n": n * nb, "invalid": int(sum(invalid)), "mismatch": 0,
                                   "steps_checked": args.steps,
                                   "reference": "host OpenSSL EVP_DigestVerify(ED25519), each step's verdict words "
@@ -399,7 +456,10 @@ def main():
     # ---- the contract's timed region: W warm-up steps + K timed steps, every step's verdict words
     # checked after it, on the GPU that has just run the flood and the 200-batch spread run above
     # (sustained operation, as a replica's verifier runs)
-    elapsed, clk_after = headline()
+    elapsed, clk_after, ver = headline()
+    if args.dump_outputs and rank == 0:
+        _dump_outputs(args.dump_outputs, ver, args.steps, n, world)
+    del ver
     value = world * n * args.steps / elapsed
     step_spread["timed_region_ms_per_step"] = elapsed / args.steps * 1e3
     gpu_clk = {"at_start": clk_before, "after_timed": clk_after, "under_load": clk_load,
@@ -730,6 +790,21 @@ def _write_detail(rec: dict) -> str:
     except OSError:
         return "unwritten"
     return os.path.relpath(path, ROOT)
+
+
+def _dump_outputs(dirname: str, ver, steps: int, n: int, world: int) -> str:
+    """--dump-outputs: what the timed path handed its caller in the last timed step, i.e. that
+    step's verdict words (at N > 1 the all-gathered words of every rank), unpacked to one float32
+    per signature (1 = accept, 0 = reject; bit i of word i // 64 is signature i): DIR/verdicts.npy,
+    shape (n,) or (world, n).  The batches are seeded, so two builds run with the same arguments
+    verify the same signatures and their files compare element for element."""
+    words = (ver.gathered if world > 1 else ver.local)[steps - 1].cpu().numpy().reshape(-1, ver.nwords)
+    bits = np.unpackbits(np.ascontiguousarray(words).view(np.uint8), axis=1, bitorder="little")[:, :n]
+    out = bits.astype(np.float32)
+    os.makedirs(dirname, exist_ok=True)
+    path = os.path.join(dirname, "verdicts.npy")
+    np.save(path, out[0] if world == 1 else out)
+    return path
 
 
 def _brief(rec, keys):

@@ -58,6 +58,41 @@ def test_parity_counts():
     assert c["config4_bls"] == {"n": 760, "mismatch": 0}
 
 
+def test_plain_and_full_options(monkeypatch):
+    """--full is off by default; --dump-outputs takes a directory; --steps / --warmup are the counts."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    a = bench.parse()
+    assert (a.full, a.dump_outputs, a.steps, a.warmup) == (False, None, 7, 3)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d"
+
+
+def test_dump_outputs_last_step_verdicts(tmp_path):
+    """DIR/verdicts.npy is the last timed step's verdict words, one float32 per signature."""
+    import numpy as np
+    import torch
+
+    import cbft_multigpu as mg
+
+    n, steps = 200, 3  # 4 words, the last one partly padding
+    rng = np.random.default_rng(5)
+    want = rng.random((steps, n)) < 0.9
+    ver = mg.StepVerdicts((n + 63) // 64, steps, 1, 0, None, torch.device("cpu"))
+    for j in range(steps):
+        ver.local[j].copy_(torch.from_numpy(mg.bools_to_words(want[j])))
+    path = bench._dump_outputs(str(tmp_path / "out"), ver, steps, n, 1)
+    got = np.load(path)
+    assert path.endswith("verdicts.npy") and got.dtype == np.float32 and got.shape == (n,)
+    assert np.array_equal(got, want[steps - 1].astype(np.float32))
+    # N > 1: every rank's gathered words of that step
+    ver2 = mg.StepVerdicts((n + 63) // 64, steps, 2, 0, None, torch.device("cpu"))
+    for r in range(2):
+        ver2.gathered[steps - 1, r].copy_(torch.from_numpy(mg.bools_to_words(want[r])))
+    got2 = np.load(bench._dump_outputs(str(tmp_path / "out2"), ver2, steps, n, 2))
+    assert got2.shape == (2, n) and np.array_equal(got2, want[:2].astype(np.float32))
+
+
 def test_line_tail_order():
     """The last keys of the line are the ones VERDICT r3 asked the driver's tail to keep."""
     src = open(os.path.join(ROOT, "bench.py")).read()

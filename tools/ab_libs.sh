@@ -9,6 +9,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out/ab
 export TMPDIR=/tmp
+BENCH_ARGS="--full ${BENCH_ARGS:-}"  # the PCIe-inclusive rate, roofline and p50 read below are --full legs
 for r in $(seq 1 "${ROUNDS:-2}"); do
   for lv in $LIBS; do
     label=${lv%%=*}; spec=${lv#*=}; lib=${spec%%@*}; envs=""

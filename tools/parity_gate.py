@@ -1,8 +1,8 @@
-"""Parity gate run by bench.py (before anything is timed) and by __graft_entry__.smoke(): every
-verdict class the GPU tests cover, checked against committed golden DATA only (no oracle import;
-the fixtures were produced by the scripts under tests/golden/).  Any mismatch raises
-ParityError, and bench.py exits non-zero, so a driver-run bench proves parity on its own even when
-the separate GPU test run is lost.
+"""Parity gate run by bench.py --full (before anything is timed) and by __graft_entry__.smoke():
+every verdict class the GPU tests cover, checked against committed golden DATA only (no oracle
+import; the fixtures were produced by the scripts under tests/golden/).  Any mismatch raises
+ParityError, and bench.py --full exits non-zero, so such a bench run proves parity on its own even
+when the separate GPU test run is lost.
 
 Classes:
   ed25519  tests/golden/ed25519_vectors.bin — 1,145 OpenSSL 3.0.2 verdicts: RFC 8032 §7.1, honest
