@@ -71,6 +71,15 @@ ABI = [
     ("cbft_ed25519_verify_fixed_device", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_ed25519_load_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _u32p]),
+    ("cbft_ed25519_signer_public_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("cbft_ed25519_unload_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    ("cbft_ed25519_sign_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_void_p]),
+    ("cbft_ed25519_sign_fixed_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_sync", ctypes.c_int, [ctypes.c_void_p]),
     ("cbft_set_profiling", ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     ("cbft_stage_times_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), ctypes.c_int]),
@@ -364,6 +373,45 @@ class Context:
 
     def sync(self):
         _check(self.lib.cbft_sync(self.handle), "cbft_sync")
+
+    # ------------------------------------------------------------------ Ed25519 signing
+    def load_signers(self, seeds) -> int:
+        """seeds: 32-byte RFC 8032 private keys; returns the signer table id."""
+        s = _as_rows(seeds, 32)
+        tid = ctypes.c_uint32()
+        _check(self.lib.cbft_ed25519_load_signers(self.handle, _ptr(s), s.shape[0], ctypes.byref(tid)),
+               "cbft_ed25519_load_signers")
+        self.__dict__.setdefault("_signer_counts", {})[tid.value] = int(s.shape[0])
+        return tid.value
+
+    def signer_public_keys(self, tid: int) -> np.ndarray:
+        """(nkeys, 32) uint8: the public keys of a table this object loaded."""
+        nkeys = self.__dict__.get("_signer_counts", {}).get(tid, 0)
+        out = np.zeros((max(1, nkeys), 32), dtype=np.uint8)
+        _check(self.lib.cbft_ed25519_signer_public_keys(self.handle, tid, _ptr(out)),
+               "cbft_ed25519_signer_public_keys")
+        return out[:nkeys]
+
+    def unload_signers(self, tid: int):
+        _check(self.lib.cbft_ed25519_unload_signers(self.handle, tid), "cbft_ed25519_unload_signers")
+
+    def sign_batch(self, tid: int, msgs: Sequence[bytes], signer_idx=None) -> np.ndarray:
+        """Signatures (n, 64) uint8 of msgs under signer_idx[i] (None: all under signer 0)."""
+        n = len(msgs)
+        blob, offs, lens = pack_messages(msgs)
+        idx = None if signer_idx is None else np.ascontiguousarray(np.asarray(signer_idx, dtype=np.uint32))
+        assert idx is None or idx.shape[0] == n
+        out = np.zeros((max(1, n), 64), dtype=np.uint8)
+        _check(self.lib.cbft_ed25519_sign_batch(self.handle, tid, None if idx is None else _ptr(idx), _ptr(blob),
+                                                 _ptr(offs), _ptr(lens), n, _ptr(out)), "cbft_ed25519_sign_batch")
+        return out[:n]
+
+    def sign_fixed_device(self, tid: int, d_signer_idx: int, d_msg: int, msg_len: int, n: int, d_sig: int,
+                          stream: int = 0):
+        """Fixed-length messages (message i at d_msg + i * msg_len); raw device addresses."""
+        _check(self.lib.cbft_ed25519_sign_fixed_device(
+            self.handle, tid, ctypes.c_void_p(d_signer_idx), ctypes.c_void_p(d_msg), msg_len, n,
+            ctypes.c_void_p(d_sig), ctypes.c_void_p(stream)), "cbft_ed25519_sign_fixed_device")
 
     # ------------------------------------------------------------------ RSA-2048 PKCS#1 v1.5 / SHA-256
     def rsa_load_keys(self, keys: Sequence[tuple]) -> int:

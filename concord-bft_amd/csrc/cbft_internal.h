@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "cbft_hipcrypto.h"
+#include "ed25519_sign.h"
 #include "ed25519_verify.h"
 #include "rsa_verify.h"
 
@@ -145,6 +146,13 @@ struct RsaKeyTable {
   DevBuf rec;
 };
 
+// Ed25519 signer table: per-signer records (clamped scalar a, prefix, public key A) derived on
+// the GPU from the seeds at load time (ed25519_sign.h CBFT_SIGNER_WORDS)
+struct SignerTable {
+  uint32_t nkeys = 0;
+  DevBuf rec;
+};
+
 struct cbft_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -227,6 +235,14 @@ struct cbft_ctx {
   bool rsa_used = false;
   hipEvent_t rsa_ev[2] = {nullptr, nullptr};  // around the last RSA kernel when profiling
   bool rsa_ev_valid = false;
+  // Ed25519 signing (cbft_ed25519_sign.cpp)
+  std::unordered_map<uint32_t, SignerTable> signer_tables;
+  uint32_t next_signer_id = 1;
+  DevBuf sign_table;                 // comb of B (ed25519_sign.h), built at the first load_signers
+  DevBuf sign_scratch;               // the batch's nonces r: secret, cleared on unload and at close
+  DevBuf sign_in, sign_out;          // packed inputs / signatures of a host-array batch
+  hipEvent_t sign_done = nullptr;    // orders reuse of sign_scratch across streams
+  bool sign_used = false;
   DevBuf bls_gen_lines, bls_msg, bls_H, bls_shares, bls_valid, bls_sig, bls_ids, bls_use, bls_lambda,
       bls_partial, bls_out, bls_ms_ok, bls_bitmap, bls_inv, bls_first, bls_flag, bls_g2tmp;
   DevBuf bls_aff;      // the last combine's signature as an affine point (BLS_SIG_WORDS)
@@ -236,6 +252,8 @@ struct cbft_ctx {
 int cbft_fail(hipError_t e, const char* what, const char* file, int line);
 // the context BLS / RSA / profiling calls run on (a multi-GPU context's first device)
 cbft_ctx* cbft_dev0(cbft_ctx* c);
+// cbft_close's part for the signing state of one device context: clears and frees it
+void cbft_sign_release(cbft_ctx* c);
 
 #define CBFT_HIP(expr)                                                          \
   do {                                                                          \

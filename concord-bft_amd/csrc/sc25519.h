@@ -131,3 +131,24 @@ __device__ __forceinline__ int sc_recode_pop(uint32_t* kp) {
   kp[0] <<= W;
   return d;
 }
+
+// s (8 words) = (r + k * a) mod L  (RFC 8032 §5.1.6 step 5): the 512-bit product plus r, reduced by
+// sc_reduce512.  r, k < L and a < 2^256, so r + k a < 2^509.  Fixed trip counts, multiplies and
+// adds only: nothing here depends on the values.
+__device__ __forceinline__ void sc_muladd(uint32_t* s, const uint32_t* r, const uint32_t* k, const uint32_t* a) {
+  uint32_t x[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) x[i] = i < 8 ? r[i] : 0u;
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    uint64_t carry = 0;
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      uint64_t t = (uint64_t)k[i] * a[j] + x[i + j] + carry;
+      x[i + j] = (uint32_t)t;
+      carry = t >> 32;
+    }
+    x[i + 8] = (uint32_t)carry;  // first write of this word
+  }
+  sc_reduce512(s, x);
+}

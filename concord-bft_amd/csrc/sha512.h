@@ -232,3 +232,36 @@ __device__ __forceinline__ void sha512_ram(uint32_t* out16, const uint32_t* R, c
     out16[2 * i + 1] = bswap32((uint32_t)H[i]);
   }
 }
+
+// h = SHA-512(prefix || M) as a 512-bit little-endian integer in 16 words: the Ed25519 signing
+// nonce hash (RFC 8032 §5.1.6 step 2), also SHA-512 of a 32-byte seed alone with len == 0.
+//   P: the 32-byte prefix as 8 little-endian 32-bit words (secret: it only ever enters W[0..3]).
+// The block count and every message address depend on len alone, which is public.
+__device__ __forceinline__ void sha512_prefix_m(uint32_t* out16, const uint32_t* P, const uint8_t* m, uint32_t len) {
+  uint64_t H[8], W[16];
+  sha512_init(H);
+  const uint32_t total = 32u + len;  // bytes hashed
+  const uint32_t nblocks = (total >> 7) + ((total & 127u) >= 112u ? 2u : 1u);
+  for (uint32_t b = 0; b < nblocks; b++) {
+    if (b == 0) {  // block 0: prefix || M[0..95]
+#pragma unroll
+      for (int j = 0; j < 4; j++) W[j] = ((uint64_t)bswap32(P[2 * j]) << 32) | bswap32(P[2 * j + 1]);
+#pragma unroll
+      for (int j = 4; j < 16; j++) W[j] = msg_word(m, len, (uint32_t)(8 * j - 32));
+    } else {
+      const uint32_t base = 128u * b - 32u;  // M-relative offset of this block
+#pragma unroll
+      for (int j = 0; j < 16; j++) W[j] = msg_word(m, len, base + 8u * j);
+    }
+    if (b == nblocks - 1) {
+      W[14] = 0;
+      W[15] = (uint64_t)total << 3;
+    }
+    sha512_compress(H, W);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; i++) {
+    out16[2 * i] = bswap32((uint32_t)(H[i] >> 32));
+    out16[2 * i + 1] = bswap32((uint32_t)H[i]);
+  }
+}

@@ -11,7 +11,11 @@
 //                                  golden vectors
 //   HipRSAVerifier : IVerifier     RSASS<PKCS1v15, SHA256> with Crypto++ 8.2.0 semantics
 //                                  (util/src/crypto_utils.cpp:101-117), 2048-bit moduli
-//   EdDSASigner : ISigner          Ed25519 signing on the host OpenSSL (signing is not the hot path)
+//   EdDSASigner : ISigner          Ed25519 signing: sign() on the host OpenSSL (one signature is
+//                                  latency-bound on any device); signBatch() on the GPU from
+//                                  CBFT_SIGN_GPU_MIN requests up (the pre-processing path signs one
+//                                  result hash per request, PreProcessReplyMsg.cpp:142-160), byte for
+//                                  byte the signatures sign() gives
 //   makeVerifier / makeSigner      the branch SigManager needs where it hard-codes RSAVerifier /
 //                                  RSASigner (SigManager.cpp:138,146,255)
 //   verifyBatch                    the batch side-API: many (verifier, data, sig) triples, one GPU
@@ -48,6 +52,18 @@ struct VerifyRequest {
   const char* sig;
   size_t sigLength;
 };
+
+// One message of a signing batch: outSig receives signatureLength() bytes.  Pointers are borrowed.
+struct SignRequest {
+  const char* data;
+  size_t dataLength;
+  char* outSig;
+};
+
+// Smallest EdDSASigner::signBatch that goes to the GPU ($CBFT_SIGN_GPU_MIN overrides): the
+// measured crossover of one cbft_ed25519_sign_batch call, host arrays in to host arrays out,
+// against a loop of sign() on one core, rounded up to a power of two.
+#define CBFT_SIGN_GPU_MIN_DEFAULT 64
 
 // A registered Ed25519 key slot: copies share the slot, the last copy releases it (a released
 // slot is reused by the next new key: rotated client keys do not grow the device table).
@@ -122,8 +138,14 @@ class EdDSASigner : public ISigner {
   ~EdDSASigner() override;
   EdDSASigner(const EdDSASigner&) = delete;
   EdDSASigner& operator=(const EdDSASigner&) = delete;
-  EdDSASigner(EdDSASigner&& o) noexcept : key_str_(std::move(o.key_str_)), pkey_(o.pkey_) { o.pkey_ = nullptr; }
+  EdDSASigner(EdDSASigner&& o) noexcept;
   std::string sign(const std::string& data) override;
+  // reqs[i].outSig = sign(reqs[i].data) for every request.  From gpuMinBatch() requests up: one
+  // cbft_ed25519_sign_batch call on the process's Ed25519 engine (the seed is registered with it
+  // at the first such batch); below it, or when the GPU call fails (counted in
+  // ed25519SignStats().gpu_errors), the host loop over sign().  Throws only where sign() throws.
+  void signBatch(const std::vector<SignRequest>& reqs);
+  static size_t gpuMinBatch();
   uint32_t signatureLength() const override { return 64; }
   std::string getPrivKey() const override { return key_str_; }
   std::string getPubKeyHex() const;
@@ -131,6 +153,9 @@ class EdDSASigner : public ISigner {
  private:
   std::string key_str_;
   void* pkey_;  // EVP_PKEY*
+  uint8_t seed_[32];                       // wiped by the destructor
+  std::shared_ptr<Ed25519Engine> engine_;  // set once the seed is registered for signBatch
+  uint32_t signer_table_ = 0;
 };
 
 enum class KeyKind { Ed25519, RSA, Unknown };
@@ -164,6 +189,14 @@ struct EngineStats {
   uint32_t table_keys;   // Ed25519 key slots on the device (live + free for reuse)
 };
 EngineStats ed25519EngineStats();
+// Signing counters of the process (they do not need an open engine).
+struct SignStats {
+  uint64_t gpu_batches;  // signBatch calls signed on the GPU
+  uint64_t gpu_items;    // signatures in them
+  uint64_t host_items;   // signatures signBatch made with the host loop
+  uint64_t gpu_errors;   // signBatch calls whose GPU path failed (signed by the host loop instead)
+};
+SignStats ed25519SignStats();
 
 // Selects the GPU the engines open (default 0; $CBFT_DEVICE overrides).  Call before the first
 // verifier is constructed.

@@ -182,6 +182,22 @@ class HipSigManager : public bftEngine::impl::SigManager {
     return first;
   }
 
+  // reqs[i].outSig = what SigManager::sign(reqs[i].data, ...) writes (getMySigLength() bytes), for
+  // every request: an Ed25519 own key signs the batch with EdDSASigner::signBatch (on the GPU from
+  // its crossover size up), an RSA one loops SigManager::sign.  The batch form of the one
+  // signature per pre-executed request of PreProcessReplyMsg::setupMsgBody
+  // (PreProcessReplyMsg.cpp:155-158) and RequestProcessingState.cpp:110,236.
+  void signBatch(const std::vector<SignRequest>& reqs) const {
+    LatencyHistogram::Scope timer(recorders().sig_manager_sign_batch);
+    if (!mySigner_) throw std::logic_error("HipSigManager::signBatch: no signing key");
+    if (auto* ed = dynamic_cast<EdDSASigner*>(mySigner_.get())) {
+      ed->signBatch(reqs);
+      return;
+    }
+    const uint16_t sigLen = getMySigLength();
+    for (const SignRequest& r : reqs) Base::sign(r.data, r.dataLength, r.outSig, sigLen);
+  }
+
   // SigManager::setClientPublicKey with a GPU verifier of the key's type.
   void setClientPublicKey(const std::string& key, PrincipalId id, Fmt format) {
     if (!replicasInfo_.isIdOfExternalClient(id) && !replicasInfo_.isIdOfClientService(id)) return;  // "Illegal id"

@@ -87,6 +87,7 @@ struct VerifyRecorders {
   LatencyHistogram rsa_verify;               // HipRSAVerifier::verify()
   LatencyHistogram verify_batch;             // concord::hip::verifyBatch(), one mixed batch
   LatencyHistogram sig_manager_batch;        // HipSigManager::verifySigBatch()
+  LatencyHistogram sig_manager_sign_batch;   // HipSigManager::signBatch()
 };
 inline VerifyRecorders& recorders() {
   static VerifyRecorders r;

@@ -255,4 +255,11 @@ std::optional<std::string> validatePreProcessResultSignatures(const char* body, 
 std::string preProcessResultHash(const char* result, uint32_t len, uint32_t resultCode, uint16_t clientId,
                                  uint64_t reqSeqNum);
 
+// PreProcessReplyMsg::setupMsgBody's signature (PreProcessReplyMsg.cpp:155-158) for the n replies
+// of one PreProcessBatchReplyMsg: outSigs[i * sigLen .. + sigLen) = the replica's signature over
+// the 32-byte result hash hashes[i * 32 .. + 32), sigLen = sigManager.getMySigLength(), with ONE
+// HipSigManager::signBatch call (the primary's RequestProcessingState.cpp:110,236 and
+// PreProcessResultMsg.cpp:83 sign the same hashes the same way).
+void signPreProcessReplyHashes(HipSigManager& sigManager, const uint8_t* hashes, size_t n, char* outSigs);
+
 }  // namespace concord::hip

@@ -414,4 +414,12 @@ std::optional<std::string> validatePreProcessResultSignatures(const char* body, 
   return std::nullopt;
 }
 
+void signPreProcessReplyHashes(HipSigManager& sm, const uint8_t* hashes, size_t n, char* outSigs) {
+  const size_t sigLen = sm.getMySigLength();
+  std::vector<SignRequest> reqs(n);
+  for (size_t i = 0; i < n; i++)
+    reqs[i] = SignRequest{reinterpret_cast<const char*>(hashes) + 32 * i, 32, outSigs + sigLen * i};
+  sm.signBatch(reqs);
+}
+
 }  // namespace concord::hip

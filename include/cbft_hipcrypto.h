@@ -65,9 +65,9 @@ int cbft_open(cbft_ctx** out, int device, size_t max_batch);
  * the verdicts land in the caller's one bitmap.  BLS key sets are loaded on every device and
  * cbft_bls_verify_shares cuts the shares into contiguous slices, one per device, verified
  * concurrently (bitmaps merged).  RSA key tables are loaded on every device and an RSA
- * host-buffer batch is sharded like an Ed25519 one.  The other BLS calls and the profiling calls
- * run on the lowest device of the mask; the _device entry points need a single-GPU context
- * (CBFT_EINVAL).
+ * host-buffer batch is sharded like an Ed25519 one.  The other BLS calls, the Ed25519 signing
+ * calls (signer tables live on that device alone) and the profiling calls run on the lowest
+ * device of the mask; the _device entry points need a single-GPU context (CBFT_EINVAL).
  * A one-bit mask is exactly cbft_open. */
 int cbft_open_mask(cbft_ctx** out, uint32_t device_mask, size_t max_batch);
 /* The same over an explicit device list, in shard order; a device may repeat (several shards,
@@ -88,6 +88,8 @@ void cbft_close(cbft_ctx* ctx);
  *   CBFT_ENGINE_INFLIGHT  per-request engine: coalesced batches in flight (host layer)
  *   CBFT_ENGINE_SPIN_US   per-request engine: waiter spin before sleeping (host layer; default 0)
  *   CBFT_EXPECTED_KEYS    key-table sizing hint of the C++ SigManager (host layer)
+ *   CBFT_SIGN_GPU_MIN     smallest EdDSASigner::signBatch that signs on the GPU (host layer;
+ *                         default CBFT_SIGN_GPU_MIN_DEFAULT in hip_crypto.hpp)
  * Geometry and scheduling switches that tests exercise on purpose (both ladder layouts, other B
  * comb radices, the three-kernel path at small sizes, ...) are per-context options, set after
  * cbft_open and before the first batch that should use them; a multi-GPU context applies them
@@ -224,6 +226,38 @@ int cbft_stage_times_ms(cbft_ctx* ctx, float* out, int nout);
  * *nbatches (nullable), how many batches were averaged.  -EINVAL unless in mode 2 with >= 1
  * batch since cbft_set_profiling. */
 int cbft_stage_times_avg_ms(cbft_ctx* ctx, float* out, int nout, int* nbatches);
+
+/* ------------------------------------------------------------------ Ed25519 signing ----------
+ * Batched RFC 8032 §5.1.6 signing, byte for byte what OpenSSL 3.0.2 EVP_DigestSign(ED25519)
+ * produces (signatures are deterministic).  It is the batch form of the one signature per
+ * pre-executed request that PreProcessReplyMsg::setupMsgBody makes
+ * (bftengine/src/preprocessor/messages/PreProcessReplyMsg.cpp:142-160).  The kernels are constant
+ * time in the private key, the prefix and the nonce (csrc/ed25519_sign.h).
+ *
+ * Load nkeys private keys: seed = nkeys x 32 bytes (RFC 8032 private keys; nkeys >= 1).  The
+ * clamped scalar, the prefix and the public key of each are derived on the GPU, once; the host
+ * staging that carried the seeds is zeroed before the call returns.  On a multi-GPU context the
+ * table lives on the lowest device. */
+int cbft_ed25519_load_signers(cbft_ctx* ctx, const uint8_t* seed, uint32_t nkeys, uint32_t* out_signer_table_id);
+/* out_pk: nkeys x 32 bytes, the public keys A = encode([a]B) of the table's signers */
+int cbft_ed25519_signer_public_keys(cbft_ctx* ctx, uint32_t signer_table_id, uint8_t* out_pk);
+/* Clears the table's secrets and the signing scratch on the device.  CBFT_EINVAL for an unknown
+ * (or already unloaded) id; cbft_close unloads what is still loaded. */
+int cbft_ed25519_unload_signers(cbft_ctx* ctx, uint32_t signer_table_id);
+/* Sign n messages (host arrays): message i = msg_blob[msg_off[i] .. + msg_len[i]) under signer
+ * signer_idx[i] (nullptr: all under signer 0); out_sig = n x 64 bytes (R || S).  Blocking.
+ * signer_idx[i] >= nkeys or msg_len[i] > 0xFFFFFF00 is CBFT_EINVAL before anything is launched,
+ * out_sig untouched; n = 0 is CBFT_OK. */
+int cbft_ed25519_sign_batch(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t* signer_idx,
+                            const uint8_t* msg_blob, const uint64_t* msg_off, const uint32_t* msg_len, size_t n,
+                            uint8_t* out_sig);
+/* Device-resident fixed-length variant (message i = d_msg[i * msg_len .. + msg_len)),
+ * asynchronous on `stream` (nullptr = the context's own stream) like
+ * cbft_ed25519_verify_fixed_device.  An out-of-range d_signer_idx entry gives 64 zero bytes.
+ * d_sig must be 4-byte aligned; single-GPU context only (CBFT_EINVAL otherwise).  Calls on
+ * different streams are ordered with each other (they share the nonce scratch). */
+int cbft_ed25519_sign_fixed_device(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t* d_signer_idx,
+                                   const uint8_t* d_msg, uint32_t msg_len, size_t n, uint8_t* d_sig, void* stream);
 
 /* ------------------------------------------------------- RSA-2048 PKCS#1 v1.5 / SHA-256 ------
  * Replaces concord::util::crypto::RSAVerifier (util/src/crypto_utils.cpp:101-117,155-168), i.e.
