@@ -1438,7 +1438,8 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
     const uint32_t pos = jj < nper ? q * nbper + (jj - naper) : 0u;
     return btbl + ((size_t)(pos < nb ? pos : 0u) * cl.b.entries() + ad) * COMB_STRIDE;
   };
-  const uint32_t wv = threadIdx.x >> 6, ln = threadIdx.x & 63u;
+  // wv through readfirstlane: the stage addresses of the entry requests (M0) stay on the scalar unit
+  const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), ln = threadIdx.x & 63u;
   auto request = [&](uint32_t slot, const uint32_t* e) {
 #pragma unroll
     for (int c = 0; c < 7; c++)
@@ -1499,13 +1500,12 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
         ypx.v[k] = neg ? ew[9 + k] : ew[k];
         ymx.v[k] = neg ? ew[k] : ew[9 + k];
       }
-      fe_sub(E, ypx, ymx);  // reduced
-      fe_add(H, ypx, ymx);
-      fe_carry(H);
-      fe_mul(P.T, E, H);
-      fe_add(P.X, E, E);
+      fe_sub_lazy(E, ypx, ymx);  // sub-lazy
+      fe_add(H, ypx, ymx);       // lazy
+      fe_mulf_oneasm(P.T, E, H);
+      fe_add(P.X, E, E);  // < 2^31.6
       fe_carry(P.X);
-      fe_add(P.Y, H, H);
+      fe_add(P.Y, H, H);  // < 2^31.001
       fe_carry(P.Y);
       fe_0(P.Z);
       P.Z.v[0] = 4;
@@ -1516,6 +1516,23 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
     // one asm statement, each instruction followed by the other product's independent one): (A, B),
     // then C alone, then (T, X) and (Y, Z).  Isolated ladder -2.3 %, 200-step headline -2 % against
     // seven single products (tools/probes/r06_ab2.sh); three- and four-way groups measured slower.
+    //
+    // The products are the fold32 multiply (fe25519.h: A B < 2^60.83 per limb pair), and a value is
+    // carried only where its products need it.  R = reduced (< 2^29 + 2^17; P's limbs and the table
+    // limbs, which the table builders leave reduced, not canonical), L = lazy (2 R), S = sub-lazy
+    // (fe_sub_lazy, < 2^30.585):
+    //   A  = s1 e1    s1 = Y + X       L x R    2^59.0
+    //   B  = s2 e2    s2 = Y - X       S x R    2^59.6    (no carry)
+    //   C  = e3 T                      R x R    2^58.0
+    //   T' = t.X t.Y  t.X = A - B, t.Y = A + B   S x L    2^60.585  (t.X not carried: the worst product)
+    //   X' = t.X t.T  t.T = s or e     S x R    2^59.6
+    //   Y' = t.Y t.Z  t.Z = e or s     L x R    2^59.0
+    //   Z' = t.Z t.T                   R x R    2^58.0
+    // s = 2Z + C (< 3 R = 2^30.585) and e = 2Z - C (< 2^31 uncarried) are carried: with t.X sub-lazy
+    // X' needs t.T < 2^30.24, which neither meets, and s e = 2^61.6 alone is too large.  Carrying
+    // t.X and e instead of s and e also fits (Y' = L x 3R = 2^60.585) with the same two passes;
+    // one pass does not: if it is e's, X' = t.X s = 2^61.17; if e stays uncarried, Z' = s e needs
+    // the pass on s and then Y' = t.Y e = L x 2^31 = 2^61.
     {
       fe A, B, C, D, s1, s2, e1, e2, e3, s, e;
 #pragma unroll
@@ -1525,11 +1542,11 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
         e3.v[k] = ew[18 + k];
       }
       fe_add(s1, P.Y, P.X);
-      fe_sub(s2, P.Y, P.X);
-      fe_mul2_oneasm(A, s1, e1, B, s2, e2);
-      fe_mul(C, e3, P.T);
+      fe_sub_lazy(s2, P.Y, P.X);
+      fe_mulf2_oneasm(A, s1, e1, B, s2, e2);
+      fe_mulf_oneasm(C, e3, P.T);
       fe_add(D, P.Z, P.Z);
-      fe_sub(t.X, A, B);
+      fe_sub_lazy(t.X, A, B);
       fe_add(t.Y, A, B);
       fe_add(s, D, C);
       fe_carry(s);
@@ -1540,8 +1557,8 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
         t.T.v[k] = neg ? s.v[k] : e.v[k];
       }
     }
-    fe_mul2_oneasm(P.T, t.X, t.Y, P.X, t.X, t.T);
-    fe_mul2_oneasm(P.Y, t.Y, t.Z, P.Z, t.Z, t.T);
+    fe_mulf2_oneasm(P.T, t.X, t.Y, P.X, t.X, t.T);
+    fe_mulf2_oneasm(P.Y, t.Y, t.Z, P.Z, t.Z, t.T);
   }
   quad_combine<0xB1>(P, false);  // P += partner lane's P
   if (live && q == 0) {

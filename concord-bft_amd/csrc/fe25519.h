@@ -15,6 +15,23 @@
 //   "reduced"  : every limb < 2^29 + 2^17        (outputs of mul/sq/carry/sub)
 //   "lazy"     : every limb < 2^30 + 2^18        (sum of two reduced)
 //   mul/sq inputs: each operand reduced or lazy.
+//
+// The fold32 multiply (fe_mulf_oneasm / fe_mulf2_oneasm, fe25519_asm_fold32.h; the pair ladder's
+// products) folds the high columns without splitting them: column k = 9..16 sums its 17 - k <= 8
+// products into its own 64-bit pair H_(k-9) with no carry-in, and the pair's register halves enter
+// the low columns as lo32(H_j) * 1216 -> column j and hi32(H_j) * 9728 -> column j + 1
+// (2^32 = 8 * 2^29; H_7's high half lands in column 8, nothing wraps).  With operand limb bounds
+// A and B the conditions are
+//   high column:  8 A B < 2^64
+//   low column 8: 9 A B + (2^32 - 1) * 9728 [H_7 high half; columns 1..7 also take (2^32 - 1) * 1216]
+//                 + carry-in (< 2^35) < 2^64,       i.e.  A B < 2^60.83
+// and the carry out of column 8 stays < 2^35, so the outputs are reduced as before (limb 1
+// < 2^29 + 2^17, the others < 2^29).  A third operand class uses that room:
+//   "sub-lazy" : limb i < 2^29 + 2^17 + m_i, m = the digits of 65p below (fe_sub_lazy: reduced -
+//                reduced, no carry pass); every limb < 1.5001 * 2^30 = 2^30.585
+// Allowed fold32 products: (reduced | lazy | sub-lazy) x (reduced | lazy); the worst, sub-lazy x lazy,
+// is 2^60.585 per product, 2^63.755 + 2^45.3 in column 8.  sub-lazy x sub-lazy (2^61.17) does NOT fit.
+// tests/test_generated_asm_fold.py runs the emitted text on exact integers at these bounds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -76,6 +93,18 @@ FE_INLINE void fe_sub(fe& r, const fe& a, const fe& b) {
 #pragma unroll
   for (int i = 1; i < FE_LIMBS; i++) r.v[i] = a.v[i] + (0x80000000u - 4u) - b.v[i];
   fe_carry(r);
+}
+
+// r = a - b (mod p) with NO carry pass: a, b reduced -> sub-lazy (a fold32 multiply takes it against
+// a reduced or lazy operand, see the bounds above).  Adds 65p = 2^261 + 2^255 - 1235 written with
+// every digit >= the reduced bound: (2^30 - 1235, 2^30 - 2 x 7, 2^29 + 2^23 - 2).  65 is the least
+// multiple with such digits: digits 1..7 of any cp are == -1 or -2 (mod 2^29), so they are
+// >= 2^29 + 2^17 only from 2^30 - 2 on, and digit 8 = c 2^23 - 2 reaches the bound at c = 65.
+FE_INLINE void fe_sub_lazy(fe& r, const fe& a, const fe& b) {
+  r.v[0] = a.v[0] + 0x3ffffb2du - b.v[0];
+#pragma unroll
+  for (int i = 1; i < FE_LIMBS - 1; i++) r.v[i] = a.v[i] + 0x3ffffffeu - b.v[i];
+  r.v[8] = a.v[8] + 0x207ffffeu - b.v[8];
 }
 
 // r = -a
@@ -146,6 +175,18 @@ FE_INLINE void fe_sq_oneasm(fe& r, const fe& a, const uint32_t* a2) {
 
 // N independent products in one statement, interleaved (tools/gen/fe25519_asm.py multi)
 #include "fe25519_asm_multi.h"
+// The fold32 multiply, single and two-way interleaved (tools/gen/fe25519_asm.py fold32): high
+// columns kept as whole 64-bit pairs and folded by their register halves (bounds at the top).
+// Its last carry (out of column 8, < 2^35) wraps by words: the low word * 1216 into limbs 0 and 1
+// with one mad, the high word (< 8, weight 2^293 = 2^32 * 2^261 == 9728 * 2^29) into limb 1.
+// Limb 1 gains < 2^13.3 + 2^16.3 < 2^17: reduced.
+FE_INLINE void fe_fold32_final(fe& r, fe& o, uint64_t acc) {
+  uint64_t w = mad64((uint32_t)acc, 1216u, (uint64_t)o.v[0]);
+  o.v[0] = (uint32_t)w & FE_MASK;
+  o.v[1] += (uint32_t)(w >> 29) + (uint32_t)(acc >> 32) * 9728u;
+  r = o;
+}
+#include "fe25519_asm_fold32.h"
 
 template <bool C = CBFT_FE_CHAIN>
 FE_INLINE void fe_mul(fe& r, const fe& a, const fe& b) {
