@@ -20,7 +20,7 @@ lib: $(LIB)
 $(CSRC)/ed25519_verify.o: $(CSRC)/ed25519_verify.hip $(CSRC)/*.h
 	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_hipcrypto.o: $(CSRC)/cbft_hipcrypto.cpp include/cbft_hipcrypto.h $(CSRC)/ed25519_verify.h $(CSRC)/cbft_internal.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h
+$(CSRC)/cbft_hipcrypto.o: $(CSRC)/cbft_hipcrypto.cpp include/cbft_hipcrypto.h $(CSRC)/ed25519_verify.h $(CSRC)/cbft_internal.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 BLS_DEPS := $(CSRC)/bls_kernels.h $(CSRC)/bls_common.h $(CSRC)/bn254_*.h $(CSRC)/row_lanes.h $(CSRC)/bls_ops.h $(CSRC)/sha256.h $(CSRC)/bls_glv.h
@@ -43,16 +43,23 @@ $(CSRC)/rsa_verify.o: $(CSRC)/rsa_verify.hip $(CSRC)/rsa_verify.h $(CSRC)/sha256
 $(CSRC)/ed25519_sign.o: $(CSRC)/ed25519_sign.hip $(CSRC)/ed25519_sign.h $(CSRC)/ge25519.h $(CSRC)/fe25519*.h $(CSRC)/sc25519.h $(CSRC)/sha512.h $(CSRC)/safegcd30.h $(CSRC)/row_lanes.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_ed25519_sign.o: $(CSRC)/cbft_ed25519_sign.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/ed25519_sign.h
+$(CSRC)/cbft_ed25519_sign.o: $(CSRC)/cbft_ed25519_sign.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_rsa.o: $(CSRC)/cbft_rsa.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h
+# RSA signing: its own object (constant-time CRT kernels; rsa_verify.hip is not touched)
+$(CSRC)/rsa_sign.o: $(CSRC)/rsa_sign.hip $(CSRC)/rsa_sign.h $(CSRC)/sha256.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(CSRC)/cbft_internal.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h include/cbft_hipcrypto.h $(CSRC)/bls_kernels.h
+$(CSRC)/cbft_rsa_sign.o: $(CSRC)/cbft_rsa_sign.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/rsa_sign.h $(CSRC)/rsa_verify.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o
+$(CSRC)/cbft_rsa.o: $(CSRC)/cbft_rsa.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(CSRC)/cbft_internal.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h include/cbft_hipcrypto.h $(CSRC)/bls_kernels.h $(CSRC)/rsa_sign.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle: $(ORACLE_LIB)
@@ -78,13 +85,16 @@ HOST_SRC := $(HOST_DIR)/src/hip_ed25519.cpp $(HOST_DIR)/src/hip_rsa.cpp $(HOST_D
 MIRROR_SRC := $(wildcard $(HOST_DIR)/ref_mirror/src/*.cpp)
 HOST_INC := -Iinclude -I$(HOST_DIR)/include -I$(HOST_DIR)/ref_mirror/include -DCBFT_WITH_CLIENT_KEYS_MAP
 HOST_HDRS := $(wildcard $(HOST_DIR)/include/*.hpp $(HOST_DIR)/include/threshsign/*.hpp $(HOST_DIR)/ref_mirror/include/*.hpp $(HOST_DIR)/ref_mirror/include/threshsign/*.h)
-host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tools/host_bench
+host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tools/host_bench
 $(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB)
 	g++ -O2 -std=c++17 -fPIC -shared -Wall $(HOST_INC) -o $@ $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN'
 tests/cpp/test_host: tests/cpp/test_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall -DCONCORD_BFT_TESTING $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_sign_host: tests/cpp/test_sign_host.cpp $(HOST_LIB)
+	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+tests/cpp/test_rsa_sign_host: tests/cpp/test_rsa_sign_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_bls_host: tests/cpp/test_bls_host.cpp $(HOST_LIB)
@@ -133,9 +143,13 @@ $(MB)/pack_probe: $(MB)/pack_probe.cpp
 # test-only device harness of the wave inversion (tests/test_inv_gpu.py; not the product library)
 SELFTEST := tests/hip/libinv_selftest.so
 SIGN_SELFTEST := tests/hip/libsign_selftest.so
-selftest: $(SELFTEST) $(SIGN_SELFTEST)
+RSA_SIGN_SELFTEST := tests/hip/librsa_sign_selftest.so
+selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST)
 $(SELFTEST): tests/hip/inv_selftest.hip $(CSRC)/safegcd30.h
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 # test-only device harness of the signing comb and sc_muladd (tests/test_ed25519_sign_gpu.py)
 $(SIGN_SELFTEST): tests/hip/sign_selftest.hip $(CSRC)/ed25519_sign.h $(CSRC)/ge25519.h $(CSRC)/fe25519*.h $(CSRC)/sc25519.h $(CSRC)/sha512.h
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
+# test-only device harness of the RSA CRT core on raw EM integers (tests/test_rsa_sign_gpu.py)
+$(RSA_SIGN_SELFTEST): tests/hip/rsa_sign_selftest.hip $(CSRC)/rsa_sign.h $(CSRC)/sha256.h
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<

@@ -95,6 +95,16 @@ ABI = [
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_rsa_kernel_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    ("cbft_rsa_load_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _u32p]),
+    ("cbft_rsa_signer_status", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("cbft_rsa_signer_moduli", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("cbft_rsa_unload_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    ("cbft_rsa_sign_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_void_p, _u32p]),
+    ("cbft_rsa_sign_fixed_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_bls_load_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32, _u32p]),
     ("cbft_bls_unload_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
     ("cbft_bls_key_status", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
@@ -454,6 +464,57 @@ class Context:
         out = ctypes.c_float()
         _check(self.lib.cbft_rsa_kernel_ms(self.handle, ctypes.byref(out)), "cbft_rsa_kernel_ms")
         return out.value
+
+    # ------------------------------------------------------------------ RSA-2048 signing (CRT)
+    def rsa_load_signers(self, keys: Sequence[tuple]) -> int:
+        """keys: (p, q, dP, dQ, qInv, e) integer tuples (1,024-bit primes in either order, qInv =
+        q^-1 mod p); returns the signer table id."""
+        priv = np.frombuffer(b"".join(int(v).to_bytes(128, "big") for k in keys for v in k[:5]), dtype=np.uint8)
+        exps = np.array([int(k[5]) for k in keys], dtype=np.uint32)
+        tid = ctypes.c_uint32()
+        _check(self.lib.cbft_rsa_load_signers(self.handle, _ptr(priv), _ptr(exps), len(keys), ctypes.byref(tid)),
+               "cbft_rsa_load_signers")
+        self.__dict__.setdefault("_rsa_signer_counts", {})[tid.value] = len(keys)
+        return tid.value
+
+    def rsa_signer_status(self, tid: int) -> np.ndarray:
+        """(nkeys,) bool: which signers of a table this object loaded are usable."""
+        nkeys = self.__dict__.get("_rsa_signer_counts", {}).get(tid, 0)
+        out = np.zeros(max(1, nkeys), dtype=np.uint8)
+        _check(self.lib.cbft_rsa_signer_status(self.handle, tid, _ptr(out)), "cbft_rsa_signer_status")
+        return out[:nkeys].astype(bool)
+
+    def rsa_signer_moduli(self, tid: int) -> list:
+        """The moduli n = p q of a table this object loaded, as integers."""
+        nkeys = self.__dict__.get("_rsa_signer_counts", {}).get(tid, 0)
+        out = np.zeros((max(1, nkeys), 256), dtype=np.uint8)
+        _check(self.lib.cbft_rsa_signer_moduli(self.handle, tid, _ptr(out)), "cbft_rsa_signer_moduli")
+        return [int.from_bytes(out[k].tobytes(), "big") for k in range(nkeys)]
+
+    def rsa_unload_signers(self, tid: int):
+        _check(self.lib.cbft_rsa_unload_signers(self.handle, tid), "cbft_rsa_unload_signers")
+        self.__dict__.get("_rsa_signer_counts", {}).pop(tid, None)
+
+    def rsa_sign_batch(self, tid: int, msgs: Sequence[bytes], signer_idx=None):
+        """(signatures (n, 256) uint8, failed): msgs signed under signer_idx[i] (None: all under
+        signer 0); failed = the number of items withheld as 256 zero bytes."""
+        n = len(msgs)
+        blob, offs, lens = pack_messages(msgs)
+        idx = None if signer_idx is None else np.ascontiguousarray(np.asarray(signer_idx, dtype=np.uint32))
+        assert idx is None or idx.shape[0] == n
+        out = np.zeros((max(1, n), 256), dtype=np.uint8)
+        failed = ctypes.c_uint32()
+        _check(self.lib.cbft_rsa_sign_batch(self.handle, tid, None if idx is None else _ptr(idx), _ptr(blob),
+                                             _ptr(offs), _ptr(lens), n, _ptr(out), ctypes.byref(failed)),
+               "cbft_rsa_sign_batch")
+        return out[:n], failed.value
+
+    def rsa_sign_fixed_device(self, tid: int, d_signer_idx: int, d_msg: int, msg_len: int, n: int, d_sig: int,
+                              stream: int = 0):
+        """Fixed-length messages (message i at d_msg + i * msg_len); raw device addresses."""
+        _check(self.lib.cbft_rsa_sign_fixed_device(
+            self.handle, tid, ctypes.c_void_p(d_signer_idx), ctypes.c_void_p(d_msg), msg_len, n,
+            ctypes.c_void_p(d_sig), ctypes.c_void_p(stream)), "cbft_rsa_sign_fixed_device")
 
     # ------------------------------------------------------------------ BLS BN-P254
     def bls_load_keys(self, pk65: bytes, vks65: Sequence[bytes]) -> int:

@@ -15,6 +15,7 @@
 #include "cbft_hipcrypto.h"
 #include "ed25519_sign.h"
 #include "ed25519_verify.h"
+#include "rsa_sign.h"
 #include "rsa_verify.h"
 
 // Pinned host staging buffer (hipHostMalloc): the host-buffer entry points pack their inputs
@@ -153,6 +154,13 @@ struct SignerTable {
   DevBuf rec;
 };
 
+// RSA signer table: per-signer CRT records (rsa_sign.h RSAS_WORDS) and, beside them, the verify
+// records of the same keys (n, e) that run the fault check
+struct RsaSignerTable {
+  uint32_t nkeys = 0;
+  DevBuf rec, vrec;
+};
+
 struct cbft_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -243,6 +251,14 @@ struct cbft_ctx {
   DevBuf sign_in, sign_out;          // packed inputs / signatures of a host-array batch
   hipEvent_t sign_done = nullptr;    // orders reuse of sign_scratch across streams
   bool sign_used = false;
+  // RSA signing (cbft_rsa_sign.cpp)
+  std::unordered_map<uint32_t, RsaSignerTable> rsa_signer_tables;
+  uint32_t next_rsa_signer_id = 1;
+  DevBuf rsas_scratch;               // the batch's window tables: secret, zeroed by the kernel, at unload and close
+  DevBuf rsas_aux, rsas_vscratch;    // fault check: idx | off | len | verdict words | count; verify scratch
+  DevBuf rsas_in, rsas_out;          // packed inputs / signatures of a host-array batch
+  hipEvent_t rsas_done = nullptr;    // orders reuse of the scratch across streams
+  bool rsas_used = false;
   DevBuf bls_gen_lines, bls_msg, bls_H, bls_shares, bls_valid, bls_sig, bls_ids, bls_use, bls_lambda,
       bls_partial, bls_out, bls_ms_ok, bls_bitmap, bls_inv, bls_first, bls_flag, bls_g2tmp;
   DevBuf bls_aff;      // the last combine's signature as an affine point (BLS_SIG_WORDS)
@@ -254,6 +270,7 @@ int cbft_fail(hipError_t e, const char* what, const char* file, int line);
 cbft_ctx* cbft_dev0(cbft_ctx* c);
 // cbft_close's part for the signing state of one device context: clears and frees it
 void cbft_sign_release(cbft_ctx* c);
+void cbft_rsa_sign_release(cbft_ctx* c);
 
 #define CBFT_HIP(expr)                                                          \
   do {                                                                          \

@@ -16,6 +16,10 @@
 //                                  CBFT_SIGN_GPU_MIN requests up (the pre-processing path signs one
 //                                  result hash per request, PreProcessReplyMsg.cpp:142-160), byte for
 //                                  byte the signatures sign() gives
+//   HipRSASigner : RSASigner       the reference's RSA signer with a batch side: sign() is the
+//                                  reference's own; signBatch() signs on the GPU (CRT, constant time,
+//                                  every signature checked before release) from
+//                                  CBFT_RSA_SIGN_GPU_MIN requests up, byte for byte what sign() gives
 //   makeVerifier / makeSigner      the branch SigManager needs where it hard-codes RSAVerifier /
 //                                  RSASigner (SigManager.cpp:138,146,255)
 //   verifyBatch                    the batch side-API: many (verifier, data, sig) triples, one GPU
@@ -158,6 +162,37 @@ class EdDSASigner : public ISigner {
   uint32_t signer_table_ = 0;
 };
 
+// Smallest HipRSASigner::signBatch that goes to the GPU ($CBFT_RSA_SIGN_GPU_MIN overrides): the
+// measured crossover of one cbft_rsa_sign_batch call, host arrays in to host arrays out, against
+// a loop of sign() on one core, rounded up to a power of two.
+#define CBFT_RSA_SIGN_GPU_MIN_DEFAULT 64
+
+// The reference's RSASigner (sign(), signatureLength(), getPrivKey() inherited unchanged) with the
+// batch form of sign().
+class HipRSASigner : public concord::util::crypto::RSASigner {
+ public:
+  // hex DER (PKCS#8 or PKCS#1) or PEM, as RSASigner takes it
+  HipRSASigner(const std::string& str_priv_key, KeyFormat fmt);
+  ~HipRSASigner() override;
+  HipRSASigner(const HipRSASigner&) = delete;
+  HipRSASigner& operator=(const HipRSASigner&) = delete;
+  // reqs[i].outSig = sign(reqs[i].data) (256 bytes for a 2,048-bit key) for every request.  From
+  // gpuMinBatch() requests up: one cbft_rsa_sign_batch call on the process's RSA engine (the CRT
+  // parameters are registered with it at the first such batch).  Below it, when the GPU call fails
+  // (counted in rsaSignStats().gpu_errors) and for the items the device's fault check withheld:
+  // sign().  A key that is not 2,048-bit two-prime with a 32-bit e never uses the GPU.
+  void signBatch(const std::vector<SignRequest>& reqs);
+  static size_t gpuMinBatch();
+  bool gpuCapable() const { return gpu_capable_; }
+
+ private:
+  bool gpu_capable_ = false;
+  uint8_t priv_[640];  // p | q | dP | dQ | qInv, big-endian; wiped by the destructor
+  uint32_t e_ = 0;
+  std::shared_ptr<RsaEngine> engine_;  // set once the key is registered for signBatch
+  uint32_t signer_table_ = 0;
+};
+
 enum class KeyKind { Ed25519, RSA, Unknown };
 // What a public-key string holds (Ed25519: raw 32 bytes or its SubjectPublicKeyInfo; RSA: an
 // RSA SubjectPublicKeyInfo), without registering it anywhere.
@@ -167,8 +202,8 @@ KeyKind privateKeyKind(const std::string& str_priv_key, KeyFormat fmt);
 // The verifier a key calls for: Ed25519 -> HipEdDSAVerifier, RSA -> HipRSAVerifier; throws
 // std::invalid_argument otherwise.
 std::shared_ptr<IVerifier> makeVerifier(const std::string& str_pub_key, KeyFormat fmt);
-// Ed25519 seed -> EdDSASigner; an RSA private key -> concord::util::crypto::RSASigner (the
-// reference's own class); throws std::invalid_argument otherwise.
+// Ed25519 seed -> EdDSASigner; an RSA private key -> HipRSASigner (the reference's own
+// concord::util::crypto::RSASigner with signBatch added); throws std::invalid_argument otherwise.
 std::unique_ptr<ISigner> makeSigner(const std::string& str_priv_key, KeyFormat fmt);
 
 // A mixed batch: one GPU launch per algorithm; any other IVerifier runs its own verify().
@@ -197,6 +232,7 @@ struct SignStats {
   uint64_t gpu_errors;   // signBatch calls whose GPU path failed (signed by the host loop instead)
 };
 SignStats ed25519SignStats();
+SignStats rsaSignStats();  // the same for HipRSASigner::signBatch
 
 // Selects the GPU the engines open (default 0; $CBFT_DEVICE overrides).  Call before the first
 // verifier is constructed.

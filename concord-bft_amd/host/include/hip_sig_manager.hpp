@@ -184,7 +184,7 @@ class HipSigManager : public bftEngine::impl::SigManager {
 
   // reqs[i].outSig = what SigManager::sign(reqs[i].data, ...) writes (getMySigLength() bytes), for
   // every request: an Ed25519 own key signs the batch with EdDSASigner::signBatch (on the GPU from
-  // its crossover size up), an RSA one loops SigManager::sign.  The batch form of the one
+  // its crossover size up), an RSA one with HipRSASigner::signBatch (the same).  The batch form of the one
   // signature per pre-executed request of PreProcessReplyMsg::setupMsgBody
   // (PreProcessReplyMsg.cpp:155-158) and RequestProcessingState.cpp:110,236.
   void signBatch(const std::vector<SignRequest>& reqs) const {
@@ -192,6 +192,10 @@ class HipSigManager : public bftEngine::impl::SigManager {
     if (!mySigner_) throw std::logic_error("HipSigManager::signBatch: no signing key");
     if (auto* ed = dynamic_cast<EdDSASigner*>(mySigner_.get())) {
       ed->signBatch(reqs);
+      return;
+    }
+    if (auto* rsa = dynamic_cast<HipRSASigner*>(mySigner_.get())) {
+      rsa->signBatch(reqs);
       return;
     }
     const uint16_t sigLen = getMySigLength();
@@ -271,7 +275,8 @@ class HipSigManager : public bftEngine::impl::SigManager {
 #else
       : Base(myId, numReplicas, rsa.myKey, rsa.keys, rsa.mapping, signing, replicasInfo) {
 #endif
-    if (!myKey.first.empty() && !mySigner_) mySigner_ = makeSigner(myKey.first, myKey.second);
+    // the base made a plain RSASigner for an RSA key: the same signer with signBatch takes its place
+    if (!myKey.first.empty()) mySigner_ = makeSigner(myKey.first, myKey.second);
     std::map<uint16_t, std::shared_ptr<concord::util::crypto::IVerifier>> byIndex;
     for (const auto& [pid, k] : mapping) {
       if (k >= keys.size()) throw std::invalid_argument("HipSigManager: key index out of range");

@@ -1,5 +1,5 @@
-// HipRSAVerifier over libcbft_hipcrypto (see hip_crypto.hpp), the mixed-batch dispatcher and
-// makeVerifier() / makeSigner().
+// HipRSAVerifier and HipRSASigner over libcbft_hipcrypto (see hip_crypto.hpp), the mixed-batch
+// dispatcher and makeVerifier() / makeSigner().
 //
 // Reference: concord::util::crypto::RSAVerifier (util/src/crypto_utils.cpp:101-117,155-168):
 // Crypto++ RSASS<PKCS1v15, SHA256> keyed from hex DER (X509PublicKey) or PEM.  Key parsing here
@@ -10,6 +10,7 @@
 #include <openssl/evp.h>
 #include <openssl/pem.h>
 
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -63,6 +64,33 @@ bool rsaPublicParts(EVP_PKEY* k, uint8_t mod[256], uint32_t* e) {
   if (ok) *e = (uint32_t)BN_get_word(be);
   BN_free(bn);
   BN_free(be);
+  return ok;
+}
+
+// p | q | dP | dQ | qInv (128 big-endian bytes each) and e of a 2,048-bit two-prime RSA key with
+// 1,024-bit primes and a 32-bit e, or false
+bool rsaCrtParts(EVP_PKEY* k, uint8_t priv[640], uint32_t* e) {
+  if (!k || EVP_PKEY_get_base_id(k) != EVP_PKEY_RSA) return false;
+  static const char* const names[5] = {OSSL_PKEY_PARAM_RSA_FACTOR1, OSSL_PKEY_PARAM_RSA_FACTOR2,
+                                       OSSL_PKEY_PARAM_RSA_EXPONENT1, OSSL_PKEY_PARAM_RSA_EXPONENT2,
+                                       OSSL_PKEY_PARAM_RSA_COEFFICIENT1};
+  BIGNUM *bn = nullptr, *be = nullptr, *extra = nullptr;
+  bool ok = EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_RSA_N, &bn) == 1 &&
+            EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_RSA_E, &be) == 1 && BN_num_bits(bn) == 2048 &&
+            BN_num_bits(be) <= 32;
+  if (ok) *e = (uint32_t)BN_get_word(be);
+  // a third prime makes it a multi-prime key: not for the two-lane CRT
+  if (ok && EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_RSA_FACTOR3, &extra) == 1) ok = false;
+  for (int i = 0; ok && i < 5; i++) {
+    BIGNUM* v = nullptr;
+    ok = EVP_PKEY_get_bn_param(k, names[i], &v) == 1 && BN_num_bits(v) <= 1024 &&
+         (i >= 2 || BN_num_bits(v) == 1024) && BN_bn2binpad(v, priv + 128 * i, 128) == 128;
+    BN_clear_free(v);
+  }
+  BN_free(bn);
+  BN_free(be);
+  BN_clear_free(extra);
+  if (!ok) OPENSSL_cleanse(priv, 640);
   return ok;
 }
 
@@ -165,6 +193,23 @@ class RsaEngine {
     for (size_t j = 0; j < n; j++) out[pos[j]] = (bitmap[j >> 3] >> (j & 7)) & 1;
   }
 
+  // Signer tables of HipRSASigner::signBatch: one per signer object, loaded at its first GPU batch.
+  // A key the device's load-time checks reject is unloaded again and reported as CBFT_EINVAL.
+  int loadSigner(const uint8_t priv[640], uint32_t e, uint32_t* id) {
+    int rc = cbft_rsa_load_signers(ctx_, priv, &e, 1, id);
+    if (rc != CBFT_OK) return rc;
+    uint8_t ok = 0;
+    rc = cbft_rsa_signer_status(ctx_, *id, &ok);
+    if (rc == CBFT_OK && !ok) rc = CBFT_EINVAL;
+    if (rc != CBFT_OK) (void)cbft_rsa_unload_signers(ctx_, *id);
+    return rc;
+  }
+  void unloadSigner(uint32_t id) { (void)cbft_rsa_unload_signers(ctx_, id); }
+  int signBatch(uint32_t id, const uint8_t* blob, const uint64_t* off, const uint32_t* len, size_t n, uint8_t* sig,
+                uint32_t* failed) {
+    return cbft_rsa_sign_batch(ctx_, id, nullptr, blob, off, len, n, sig, failed);
+  }
+
  private:
   static constexpr uint32_t kNoTable = 0;  // table ids start at 1
   RsaEngine() {
@@ -245,6 +290,99 @@ void HipRSAVerifier::verifyBatch(const std::vector<VerifyRequest>& reqs, std::ve
     }
 }
 
+// ---------------------------------------------------------------------------------- signer
+static std::atomic<uint64_t> g_rsa_sign_gpu_batches{0}, g_rsa_sign_gpu_items{0}, g_rsa_sign_host_items{0},
+    g_rsa_sign_gpu_errors{0};
+static std::mutex g_rsa_sign_register_mu;  // one signer registers its key at a time
+
+SignStats rsaSignStats() {
+  return SignStats{g_rsa_sign_gpu_batches.load(), g_rsa_sign_gpu_items.load(), g_rsa_sign_host_items.load(),
+                   g_rsa_sign_gpu_errors.load()};
+}
+
+HipRSASigner::HipRSASigner(const std::string& str_priv_key, KeyFormat fmt)
+    : concord::util::crypto::RSASigner(str_priv_key, fmt) {
+  EVP_PKEY* k = parsePrivateKey(str_priv_key, fmt);
+  gpu_capable_ = rsaCrtParts(k, priv_, &e_);
+  EVP_PKEY_free(k);
+}
+
+HipRSASigner::~HipRSASigner() {
+  if (engine_) engine_->unloadSigner(signer_table_);
+  OPENSSL_cleanse(priv_, sizeof priv_);
+}
+
+size_t HipRSASigner::gpuMinBatch() {
+  static const size_t v = [] {
+    const char* e = std::getenv("CBFT_RSA_SIGN_GPU_MIN");
+    const long long x = e ? std::atoll(e) : 0;
+    return x > 0 ? (size_t)x : (size_t)CBFT_RSA_SIGN_GPU_MIN_DEFAULT;
+  }();
+  return v;
+}
+
+void HipRSASigner::signBatch(const std::vector<SignRequest>& reqs) {
+  const size_t n = reqs.size();
+  if (n == 0) return;
+  const size_t sl = signatureLength();
+  std::vector<bool> done(n, false);
+  size_t on_gpu = 0;
+  if (gpu_capable_ && n >= gpuMinBatch()) {
+    try {
+      {
+        std::lock_guard<std::mutex> g(g_rsa_sign_register_mu);
+        if (!engine_) {
+          auto engine = RsaEngine::get();  // throws when the engine cannot be opened
+          uint32_t id = 0;
+          const int rc = engine->loadSigner(priv_, e_, &id);
+          if (rc != CBFT_OK) throw std::runtime_error("cbft_rsa_load_signers");
+          engine_ = std::move(engine);
+          signer_table_ = id;
+        }
+      }
+      size_t blob = 0;
+      bool fits = true;
+      for (const SignRequest& r : reqs) {
+        fits = fits && r.dataLength <= 0xFFFFFF00u;
+        blob += r.dataLength;
+      }
+      if (!fits) throw std::runtime_error("message too long for the GPU signer");
+      std::vector<uint8_t> msg(blob ? blob : 1), sig(n * 256);
+      std::vector<uint64_t> off(n);
+      std::vector<uint32_t> len(n);
+      size_t o = 0;
+      for (size_t i = 0; i < n; i++) {
+        off[i] = o;
+        len[i] = (uint32_t)reqs[i].dataLength;
+        if (reqs[i].dataLength) std::memcpy(&msg[o], reqs[i].data, reqs[i].dataLength);
+        o += reqs[i].dataLength;
+      }
+      uint32_t failed = 0;
+      const int rc = engine_->signBatch(signer_table_, msg.data(), off.data(), len.data(), n, sig.data(), &failed);
+      if (rc != CBFT_OK) throw std::runtime_error("cbft_rsa_sign_batch");
+      // a withheld signature is 256 zero bytes (no signature is: s = 0 only for EM = 0)
+      static const uint8_t zero[256] = {};
+      for (size_t i = 0; i < n; i++) {
+        if (failed && std::memcmp(&sig[256 * i], zero, 256) == 0) continue;  // signed below, on the host
+        std::memcpy(reqs[i].outSig, &sig[256 * i], 256);
+        done[i] = true;
+        on_gpu++;
+      }
+      g_rsa_sign_gpu_batches++;
+      g_rsa_sign_gpu_items += on_gpu;
+    } catch (...) {
+      g_rsa_sign_gpu_errors++;  // the signatures are still produced, below
+    }
+  }
+  if (on_gpu == n) return;
+  for (size_t i = 0; i < n; i++) {
+    if (done[i]) continue;
+    const std::string s = sign(std::string(reqs[i].data, reqs[i].dataLength));
+    std::memcpy(reqs[i].outSig, s.data(), std::min(sl, s.size()));
+  }
+  g_rsa_sign_host_items += n - on_gpu;
+}
+
 // ---------------------------------------------------------------------------------- dispatch
 KeyKind publicKeyKind(const std::string& str_pub_key, KeyFormat fmt) {
   uint8_t raw[32];
@@ -281,7 +419,7 @@ std::unique_ptr<ISigner> makeSigner(const std::string& str_priv_key, KeyFormat f
     case KeyKind::Ed25519:
       return std::make_unique<EdDSASigner>(str_priv_key, fmt);
     case KeyKind::RSA:
-      return std::make_unique<concord::util::crypto::RSASigner>(str_priv_key, fmt);
+      return std::make_unique<HipRSASigner>(str_priv_key, fmt);
     default:
       throw std::invalid_argument("makeSigner: neither an Ed25519 nor an RSA private key");
   }

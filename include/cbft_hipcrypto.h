@@ -65,8 +65,8 @@ int cbft_open(cbft_ctx** out, int device, size_t max_batch);
  * the verdicts land in the caller's one bitmap.  BLS key sets are loaded on every device and
  * cbft_bls_verify_shares cuts the shares into contiguous slices, one per device, verified
  * concurrently (bitmaps merged).  RSA key tables are loaded on every device and an RSA
- * host-buffer batch is sharded like an Ed25519 one.  The other BLS calls, the Ed25519 signing
- * calls (signer tables live on that device alone) and the profiling calls run on the lowest
+ * host-buffer batch is sharded like an Ed25519 one.  The other BLS calls, the Ed25519 and RSA
+ * signing calls (signer tables live on that device alone) and the profiling calls run on the lowest
  * device of the mask; the _device entry points need a single-GPU context (CBFT_EINVAL).
  * A one-bit mask is exactly cbft_open. */
 int cbft_open_mask(cbft_ctx** out, uint32_t device_mask, size_t max_batch);
@@ -90,6 +90,8 @@ void cbft_close(cbft_ctx* ctx);
  *   CBFT_EXPECTED_KEYS    key-table sizing hint of the C++ SigManager (host layer)
  *   CBFT_SIGN_GPU_MIN     smallest EdDSASigner::signBatch that signs on the GPU (host layer;
  *                         default CBFT_SIGN_GPU_MIN_DEFAULT in hip_crypto.hpp)
+ *   CBFT_RSA_SIGN_GPU_MIN smallest HipRSASigner::signBatch that signs on the GPU (host layer;
+ *                         default CBFT_RSA_SIGN_GPU_MIN_DEFAULT in hip_crypto.hpp)
  * Geometry and scheduling switches that tests exercise on purpose (both ladder layouts, other B
  * comb radices, the three-kernel path at small sizes, ...) are per-context options, set after
  * cbft_open and before the first batch that should use them; a multi-GPU context applies them
@@ -292,6 +294,48 @@ int cbft_rsa_verify_batch_device(cbft_ctx* ctx, uint32_t key_table_id, const uin
                                  const uint32_t* d_msg_len, size_t n, uint64_t* d_verdict_words, void* stream);
 /* With profiling enabled (cbft_set_profiling): the last RSA verify kernel's duration in ms. */
 int cbft_rsa_kernel_ms(cbft_ctx* ctx, float* out_ms);
+
+/* ------------------------------------------------------------ RSA-2048 signing (CRT) ---------
+ * Batched PKCS#1 v1.5 / SHA-256 signing, byte for byte what OpenSSL 3.0.2 EVP_DigestSign (RSA,
+ * SHA-256) and the reference's RSASigner (Crypto++ RSASS<PKCS1v15, SHA256>::Signer) produce
+ * (signatures are deterministic; oracle/rsa_ref.py:sign).  The batch form of ISigner::sign for an
+ * RSA replica key.  The kernels are constant time in p, q, dP, dQ, qInv and every intermediate
+ * (csrc/rsa_sign.h), and every signature is checked with the public operation (s^e mod n == EM)
+ * before it leaves the device.
+ *
+ * Load nkeys private keys: priv = nkeys x 640 bytes, p | q | dP | dQ | qInv of 128 bytes big-endian
+ * each (either prime order); exponents = the nkeys public exponents.  The records are built on the
+ * GPU, once; the host staging that carried the keys is zeroed before the call returns.  A key is
+ * usable (cbft_rsa_signer_status) only if p and q are odd, exactly 1,024 bits and different, n = p q
+ * is exactly 2,048 bits, qInv q = 1 (mod p) and a signature made under it at load verifies.  Any
+ * other key is accepted into the table and every signature under it is 256 zero bytes.  On a
+ * multi-GPU context the table lives on the lowest device. */
+#define CBFT_RSA_PRIVATE_KEY_BYTES 640
+int cbft_rsa_load_signers(cbft_ctx* ctx, const uint8_t* priv, const uint32_t* exponents, uint32_t nkeys,
+                          uint32_t* out_signer_table_id);
+/* out_ok: nkeys bytes, 1 = the signer is usable */
+int cbft_rsa_signer_status(cbft_ctx* ctx, uint32_t signer_table_id, uint8_t* out_ok);
+/* out_n: nkeys x 256 bytes big-endian, the moduli n = p q of the table's signers */
+int cbft_rsa_signer_moduli(cbft_ctx* ctx, uint32_t signer_table_id, uint8_t* out_n);
+/* Clears the table's secrets and the signing scratch on the device.  CBFT_EINVAL for an unknown
+ * (or already unloaded) id; cbft_close unloads what is still loaded. */
+int cbft_rsa_unload_signers(cbft_ctx* ctx, uint32_t signer_table_id);
+/* Sign n messages (host arrays): message i = msg_blob[msg_off[i] .. + msg_len[i]) under signer
+ * signer_idx[i] (nullptr: all under signer 0); out_sig = n x 256 bytes big-endian.  Blocking.
+ * signer_idx[i] >= nkeys or msg_len[i] > 0xFFFFFF00 is CBFT_EINVAL before anything is launched,
+ * out_sig untouched; n = 0 is CBFT_OK.  *out_failed (nullable) = the number of items whose
+ * signature was withheld (256 zero bytes): those under an unusable signer and those that did not
+ * pass the check s^e mod n == EM.  The caller signs such items some other way. */
+int cbft_rsa_sign_batch(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t* signer_idx, const uint8_t* msg_blob,
+                        const uint64_t* msg_off, const uint32_t* msg_len, size_t n, uint8_t* out_sig,
+                        uint32_t* out_failed);
+/* Device-resident fixed-length variant (message i = d_msg[i * msg_len .. + msg_len)),
+ * asynchronous on `stream` (nullptr = the context's own stream).  An out-of-range d_signer_idx
+ * entry, an unusable signer or a failed check gives 256 zero bytes.  d_sig must be 4-byte aligned;
+ * single-GPU context only (CBFT_EINVAL otherwise).  Calls on different streams are ordered with
+ * each other (they share the window-table scratch). */
+int cbft_rsa_sign_fixed_device(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t* d_signer_idx,
+                               const uint8_t* d_msg, uint32_t msg_len, size_t n, uint8_t* d_sig, void* stream);
 
 /* ------------------------------------------------------------- BLS BN-P254 (threshsign) ------
  * RELIC "BN_P254" curve (threshsign/src/bls/relic/Library.cpp:51,72): G1 compressed = 33 bytes,
