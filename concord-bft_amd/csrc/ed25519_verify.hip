@@ -1378,6 +1378,111 @@ __global__ void __launch_bounds__(SMALL3_BLOCK) ed25519_small3_kernel(const Ed25
 #define COMB2_BLOCK 128
 #define COMB2_MAX_STEPS 24  // additions per lane: radix-2^8 keys + radix-2^16 B = 48 positions
 #define COMB2_MIN_WAVES 2
+
+// Lane role of a pair (q = threadIdx.x & 1) as a mask LLVM cannot see through: all ones in lane 1.
+// With plain ternaries on q it would merge the limb-wise selects into divergent branches (as in
+// bn254_cycsq.h cs_mask); with the mask every select is one v_bfi_b32.
+__device__ __forceinline__ uint32_t pair_mask(uint32_t q) {
+  uint32_t m = 0u - q;
+  asm volatile("" : "+v"(m));
+  return m;
+}
+// r = m ? a : b, limb-wise
+__device__ __forceinline__ void fe_sel(fe& r, uint32_t m, const fe& a, const fe& b) {
+#pragma unroll
+  for (int k = 0; k < FE_LIMBS; k++) r.v[k] = (a.v[k] & m) | (b.v[k] & ~m);
+}
+
+// fe_dpp for a quad_perm with the whole wave active: every lane has a source lane, so bound_ctrl
+// changes no value, and with it set the compiler drops the `old` operand's initialisation (one
+// v_mov_b32 per limb in front of each v_mov_b32_dpp).
+template <int CTRL>
+__device__ __forceinline__ void fe_dpp_quad(fe& r, const fe& a) {
+#pragma unroll
+  for (int k = 0; k < FE_LIMBS; k++)
+    r.v[k] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)a.v[k], CTRL, 0xF, 0xF, true);
+}
+
+// The pair ladder's closing sum P0 + P1 (lane 0 holds P0, lane 1 holds P1), computed ONCE and split
+// over the two lanes: the unified a = -1 addition of ge_add (complete: the partial sums may be the
+// identity, equal or opposite), its 8 products in 4 product slots per lane instead of 8 in each
+// (quad_combine<0xB1>).  Lane 0 ends with (X3 : Y3 : Z3); lane 1's P is left meaningless.  No T.
+//
+//   slot   lane 0                          lane 1
+//   1      Zz = Z0 Z1                      K  = T1 2d
+//   2      A  = (Y0 - X0)(Y1 - X1)         C  = K T0
+//   3      B  = (Y0 + X0)(Y1 + X1)         Z3 = F G       D = 2 Zz, F = D - C, G = D + C
+//   4      X3 = E F    E = B - A           Y3 = G H       H = B + A
+//
+// Zz and K come first so that C, and with it F and G, are ready one slot before E and H: Z3 fills
+// the slot lane 1 would idle in while lane 0 forms B (5 slots with A, B first).  Both lanes issue the
+// same instructions; operands are picked by role with pair_mask selects, and a value the partner
+// holds arrives by DPP quad_perm 0xB1, where possible as ONE exchange of a role-selected value
+// (lane 1 offers what lane 0 needs and the reverse).  Single products: pairing two of a lane's
+// products in one statement would need two independent products per lane per slot pair, which only
+// the 5-slot order has.
+//
+// Products are the fold32 multiply (fe25519.h: A B < 2^60.83 per limb pair).  R = reduced
+// (< 2^29 + 2^17: P's limbs, products, carried values, the constant 2d), L = lazy (2 R),
+// S = sub-lazy (fe_sub_lazy, < 2^30.585):
+//   Zz = Z0 Z1                            R x R    2^58.0
+//   K  = T1 2d                            R x R    2^58.0
+//   A  = (Y0 - X0) (Y1 - X1)              S x R    2^59.6    Y1 - X1 carried: S x S = 2^61.17 does not fit
+//   C  = K T0                             R x R    2^58.0
+//   B  = (Y0 + X0) (Y1 + X1)              L x L    2^60.001  (neither carried)
+//   Z3 = F G                              R x R    2^58.0    both carried: D - C uncarried is < 2^31,
+//   X3 = E F      E = B - A uncarried     S x R    2^59.6      G = D + C < 3 R, and 2^31 x 3 R = 2^61.6;
+//   Y3 = G H      H = B + A               R x L    2^59.0      one of them uncarried would move its pass to E
+// Three carry passes (Y - X, F, G) against quad_combine's six in each lane.
+__device__ __forceinline__ void pair_combine_split(ge_p3& P, uint32_t q) {
+  const uint32_t m = pair_mask(q);
+  fe a, b, w, r1, r2, r3, r4;
+  {  // slot 1
+    fe d2;
+    fe_load_const(d2, kFeD2);
+    fe_dpp_quad<0xB1>(w, P.Z);
+    fe_sel(a, m, P.T, P.Z);
+    fe_sel(b, m, d2, w);
+    fe_mulf_oneasm(r1, a, b);  // Zz | K
+  }
+  {  // slot 2
+    fe dl, dc;
+    fe_sub_lazy(dl, P.Y, P.X);  // S
+    dc = dl;
+    fe_carry(dc);               // R
+    fe_sel(w, m, dc, P.T);      // lane 1 offers Y1 - X1, lane 0 offers T0
+    fe_dpp_quad<0xB1>(b, w);
+    fe_sel(a, m, r1, dl);
+    fe_mulf_oneasm(r2, a, b);   // A | C
+  }
+  fe F, G;
+  {  // slot 3
+    fe s, sp, D;
+    fe_add(s, P.Y, P.X);  // L
+    fe_dpp_quad<0xB1>(sp, s);
+    fe_dpp_quad<0xB1>(D, r1);  // lane 1: Zz
+    fe_add(D, D, D);      // L
+    fe_add(G, D, r2);     // 3 R
+    fe_carry(G);          // R
+    fe_sub(F, D, r2);     // R
+    fe_sel(a, m, F, s);
+    fe_sel(b, m, G, sp);
+    fe_mulf_oneasm(r3, a, b);  // B | Z3
+  }
+  {  // slot 4
+    fe E, H;
+    fe_sub_lazy(E, r3, r2);  // lane 0: B - A, S
+    fe_add(H, r3, r2);       // lane 0: B + A, L
+    fe_sel(w, m, F, H);      // lane 1 offers F, lane 0 offers H
+    fe_dpp_quad<0xB1>(b, w);
+    fe_sel(a, m, G, E);
+    fe_mulf_oneasm(r4, a, b);  // X3 | Y3
+  }
+  P.X = r4;
+  fe_dpp_quad<0xB1>(P.Y, r4);
+  fe_dpp_quad<0xB1>(P.Z, r3);
+}
+
 __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
     ed25519_comb2_ladder_kernel(const Ed25519Batch b, const uint32_t* h_soa, const uint32_t* btbl,
                                 const CombLadder cl, uint32_t* xyz_soa) {
@@ -1560,7 +1665,7 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
     fe_mulf2_oneasm(P.T, t.X, t.Y, P.X, t.X, t.T);
     fe_mulf2_oneasm(P.Y, t.Y, t.Z, P.Z, t.Z, t.T);
   }
-  quad_combine<0xB1>(P, false);  // P += partner lane's P
+  pair_combine_split(P, q);  // lane 0: P += partner lane's P (X, Y, Z)
   if (live && q == 0) {
     fe_store_soa(xyz_soa, b.n, i, P.X);
     fe_store_soa(xyz_soa + 9 * b.n, b.n, i, P.Y);

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Opcode histogram of a kernel's hottest loop body from an llvm-objdump listing.
 
-    python3 tools/isa/isa_hist.py <listing.s> <kernel-substring> [--all | --loops]
+    python3 tools/isa/isa_hist.py <listing.s> <kernel-substring> [--all | --tail | --loops]
 
 The loop is the instruction range [target, branch] of the backward s_cbranch / s_branch that spans
-the most instructions (the ladder's step loop); --all histograms the whole kernel instead; --loops
+the most instructions (the ladder's step loop); --all histograms the whole kernel instead; --tail
+everything from the last backward branch to s_endpgm (the pair ladder's closing sum and store); --loops
 lists every loop (start address, instructions, scalar / vector / 64-bit mad / DPP / readlane counts)."""
 import re
 import sys
@@ -52,12 +53,17 @@ def main():
                   f"mad64 {c['v_mad_u64_u32'] + c['v_mad_i64_i32']:4d}  dpp {c['v_mov_b32_dpp']:3d}  "
                   f"readlane {c['v_readlane_b32']:3d}")
         return
-    if "--all" not in sys.argv and loops:
+    where = "kernel"
+    if "--tail" in sys.argv and loops:
+        hi = max(h for _, h in loops)  # blocks laid out behind the step loop branch back into it
+        end = max(k for k, x in enumerate(insns) if x[1] == "s_endpgm")  # drop the padding behind it
+        body, where = insns[hi + 1:end + 1], "tail (after the last backward branch)"
+    elif "--all" not in sys.argv and loops:
         lo, hi = max(loops, key=lambda x: x[1] - x[0])
-        body = insns[lo:hi + 1]
+        body, where = insns[lo:hi + 1], "loop body"
     h = Counter(op for _, op, _ in body)
     total = sum(h.values())
-    print(f"{name}: {total} instructions in the {'kernel' if body is insns else 'loop body'}")
+    print(f"{name}: {total} instructions in the {where}")
     for op, c in h.most_common():
         print(f"{c:6d}  {100.0 * c / total:5.1f}%  {op}")
 
