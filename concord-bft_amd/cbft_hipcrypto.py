@@ -126,6 +126,15 @@ ABI = [
     ("cbft_bls_sign", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p,
                                      ctypes.c_uint32, ctypes.c_void_p]),
     ("cbft_bls_public_key", ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p]),
+    ("cbft_bls_load_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _u32p]),
+    ("cbft_bls_signer_public_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("cbft_bls_unload_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    ("cbft_bls_sign_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_void_p]),
+    ("cbft_bls_sign_fixed_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_bls_combine_partial", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
       ctypes.c_void_p]),
@@ -608,6 +617,46 @@ class Context:
         _check(self.lib.cbft_bls_sign(self.handle, sk.to_bytes(32, "big"), share_id, msg, len(msg), out),
                "cbft_bls_sign")
         return out.raw
+
+    def load_bls_signers(self, sks: Sequence[int], ids: Sequence[int]) -> int:
+        """sks: secret scalars, ids: their share ids (1 .. 2048); returns the signer table id."""
+        assert len(sks) == len(ids) and len(sks) > 0
+        sk = np.frombuffer(b"".join(int(k).to_bytes(32, "big") for k in sks), dtype=np.uint8).copy()
+        idv = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32))
+        tid = ctypes.c_uint32()
+        rc = self.lib.cbft_bls_load_signers(self.handle, _ptr(sk), _ptr(idv), len(sks), ctypes.byref(tid))
+        sk[:] = 0
+        _check(rc, "cbft_bls_load_signers")
+        self.__dict__.setdefault("_bls_signer_counts", {})[tid.value] = len(sks)
+        return tid.value
+
+    def bls_signer_public_keys(self, tid: int) -> List[bytes]:
+        """The 65-byte share verification keys of a table this object loaded."""
+        nkeys = self.__dict__.get("_bls_signer_counts", {}).get(tid, 0)
+        out = np.zeros((max(1, nkeys), 65), dtype=np.uint8)
+        _check(self.lib.cbft_bls_signer_public_keys(self.handle, tid, _ptr(out)), "cbft_bls_signer_public_keys")
+        return [out[i].tobytes() for i in range(nkeys)]
+
+    def unload_bls_signers(self, tid: int):
+        _check(self.lib.cbft_bls_unload_signers(self.handle, tid), "cbft_bls_unload_signers")
+
+    def bls_sign_batch(self, tid: int, msgs: Sequence[bytes], signer_idx=None) -> np.ndarray:
+        """Shares (n, 37) uint8 of msgs under signer_idx[i] (None: all under signer 0)."""
+        n = len(msgs)
+        blob, offs, lens = pack_messages(msgs)
+        idx = None if signer_idx is None else np.ascontiguousarray(np.asarray(signer_idx, dtype=np.uint32))
+        assert idx is None or idx.shape[0] == n
+        out = np.zeros((max(1, n), 37), dtype=np.uint8)
+        _check(self.lib.cbft_bls_sign_batch(self.handle, tid, None if idx is None else _ptr(idx), _ptr(blob),
+                                            _ptr(offs), _ptr(lens), n, _ptr(out)), "cbft_bls_sign_batch")
+        return out[:n]
+
+    def bls_sign_fixed_device(self, tid: int, d_signer_idx: int, d_msg: int, msg_len: int, n: int, d_out37: int,
+                              stream: int = 0):
+        """Fixed-length messages (message i at d_msg + i * msg_len); raw device addresses."""
+        _check(self.lib.cbft_bls_sign_fixed_device(
+            self.handle, tid, ctypes.c_void_p(d_signer_idx), ctypes.c_void_p(d_msg), msg_len, n,
+            ctypes.c_void_p(d_out37), ctypes.c_void_p(stream)), "cbft_bls_sign_fixed_device")
 
     def bls_public_key(self, sk: int) -> bytes:
         """sk * g2, 65 compressed bytes (the signer's share verification key)."""

@@ -539,6 +539,16 @@ static bool scalar_mod_r(uint32_t* w) {
   return any != 0;
 }
 
+}  // extern "C"
+
+// the same conversion for the signer tables of cbft_bls_sign.cpp (cbft_internal.h)
+bool cbft_bls_scalar_words(uint32_t* w, const uint8_t* sk32) {
+  be32_scalar_words(w, sk32);
+  return scalar_mod_r(w);
+}
+
+extern "C" {
+
 int cbft_bls_public_key(cbft_ctx* c, const uint8_t* sk32, uint8_t* out65) {
   c = cbft_dev0(c);
   if (!c || !sk32 || !out65) return CBFT_EINVAL;

@@ -161,6 +161,14 @@ struct RsaSignerTable {
   DevBuf rec, vrec;
 };
 
+// BLS signer table: per-signer records (GLV halves' digit words, signs, odd fixes, id:
+// bls_sign_batch.h BLS_SIGNER_WORDS) built on the GPU at load time, and the signers' public keys
+// vk = sk * g2 (not secret) computed by the same load
+struct BlsSignerTable {
+  uint32_t nkeys = 0;
+  DevBuf rec, vk65;
+};
+
 struct cbft_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -259,6 +267,13 @@ struct cbft_ctx {
   DevBuf rsas_in, rsas_out;          // packed inputs / signatures of a host-array batch
   hipEvent_t rsas_done = nullptr;    // orders reuse of the scratch across streams
   bool rsas_used = false;
+  // BLS share signing in batches (cbft_bls_sign.cpp)
+  std::unordered_map<uint32_t, BlsSignerTable> bls_signer_tables;
+  uint32_t next_bls_signer_id = 1;
+  DevBuf blss_scratch;               // the batch's hash points (public)
+  DevBuf blss_in, blss_out;          // packed inputs / shares of a host-array batch
+  hipEvent_t blss_done = nullptr;    // orders reuse of the scratch across streams
+  bool blss_used = false;
   DevBuf bls_gen_lines, bls_msg, bls_H, bls_shares, bls_valid, bls_sig, bls_ids, bls_use, bls_lambda,
       bls_partial, bls_out, bls_ms_ok, bls_bitmap, bls_inv, bls_first, bls_flag, bls_g2tmp;
   DevBuf bls_aff;      // the last combine's signature as an affine point (BLS_SIG_WORDS)
@@ -271,6 +286,10 @@ cbft_ctx* cbft_dev0(cbft_ctx* c);
 // cbft_close's part for the signing state of one device context: clears and frees it
 void cbft_sign_release(cbft_ctx* c);
 void cbft_rsa_sign_release(cbft_ctx* c);
+void cbft_bls_sign_release(cbft_ctx* c);
+// 32-byte big-endian BLS scalar -> 8 little-endian words reduced mod r, as cbft_bls_sign takes it;
+// false for 0 (mod r)
+bool cbft_bls_scalar_words(uint32_t* w, const uint8_t* sk32);
 
 #define CBFT_HIP(expr)                                                          \
   do {                                                                          \

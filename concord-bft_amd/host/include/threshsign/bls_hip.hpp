@@ -23,6 +23,7 @@
 
 #include <array>
 #include <memory>
+#include <mutex>
 #include <string>
 #include <vector>
 
@@ -140,6 +141,20 @@ class BlsMultisigAccumulator : public BlsAccumulatorBase {
   void getFullSignedData(char* outThreshSig, int threshSigLen) override;
 };
 
+// One share to sign in BlsThresholdSigner::signBatch: out receives 37 bytes (outLen >= 37).
+struct BlsSignRequest {
+  const char* hash;
+  int hashLen;
+  char* out;
+  int outLen;
+};
+
+// Smallest BlsThresholdSigner::signBatch that signs in ONE cbft_bls_sign_batch call
+// ($CBFT_BLS_SIGN_BATCH_MIN overrides); smaller batches loop cbft_bls_sign.  Both run on the GPU (the
+// product path has no CPU signer).  The measured crossover of one batch call against n lone calls,
+// host arrays in to host arrays out.
+#define CBFT_BLS_SIGN_BATCH_MIN_DEFAULT 8
+
 class BlsThresholdSigner : public IThresholdSigner {
  public:
   // vkHex empty: the verification key is derived from the secret key on the GPU (sk * g2), as
@@ -148,6 +163,14 @@ class BlsThresholdSigner : public IThresholdSigner {
   int requiredLengthForSignedData() const override { return 37; }
   // outSig = 4-byte big-endian id || sk * H(hash); throws std::runtime_error if outSigLen < 37
   void signData(const char* hash, int hashLen, char* outSig, int outSigLen) override;
+  // The batch form of signData for the shares of several sequence numbers in flight: every out gets
+  // the bytes signData gives for its hash.  The key is registered in a signer table of the engine at
+  // the first batch of batchMin() requests or more.  Throws as signData does, before anything is signed.
+  void signBatch(const std::vector<BlsSignRequest>& requests);
+  static size_t batchMin();
+  ~BlsThresholdSigner() override;
+  BlsThresholdSigner(const BlsThresholdSigner&) = delete;
+  BlsThresholdSigner& operator=(const BlsThresholdSigner&) = delete;
   const IShareSecretKey& getShareSecretKey() const override { return sk_; }
   const IShareVerificationKey& getShareVerificationKey() const override { return vk_; }
 
@@ -156,6 +179,8 @@ class BlsThresholdSigner : public IThresholdSigner {
   BlsSecretKey sk_;
   BlsPublicKey vk_;
   std::shared_ptr<BlsEngine> engine_;
+  std::mutex table_mu_;        // guards the registration below (concurrent first batches)
+  uint32_t signer_table_ = 0;  // one-key table of the engine's context, loaded by the first GPU batch
 };
 
 }  // namespace Hip

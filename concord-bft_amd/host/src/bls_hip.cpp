@@ -338,5 +338,50 @@ void BlsThresholdSigner::signData(const char* hash, int hashLen, char* outSig, i
         "cbft_bls_sign");
 }
 
+BlsThresholdSigner::~BlsThresholdSigner() {
+  if (signer_table_) (void)cbft_bls_unload_signers(engine_->ctx(), signer_table_);
+}
+
+size_t BlsThresholdSigner::batchMin() {
+  static const size_t v = [] {
+    const char* e = std::getenv("CBFT_BLS_SIGN_BATCH_MIN");
+    const long long x = e ? std::atoll(e) : 0;
+    return x > 0 ? (size_t)x : (size_t)CBFT_BLS_SIGN_BATCH_MIN_DEFAULT;
+  }();
+  return v;
+}
+
+void BlsThresholdSigner::signBatch(const std::vector<BlsSignRequest>& requests) {
+  for (const auto& r : requests) {
+    if (!r.out || r.outLen < 37) throw std::runtime_error("BLS signer: output buffer shorter than 37 bytes");
+    if (!r.hash || r.hashLen < 0) throw std::invalid_argument("BLS signer: no message");
+  }
+  const size_t n = requests.size();
+  if (n < batchMin()) {
+    for (const auto& r : requests) signData(r.hash, r.hashLen, r.out, r.outLen);
+    return;
+  }
+  {
+    std::lock_guard<std::mutex> g(table_mu_);
+    if (!signer_table_) {
+      const uint32_t id = (uint32_t)id_;
+      check(cbft_bls_load_signers(engine_->ctx(), sk_.bytes().data(), &id, 1, &signer_table_), "cbft_bls_load_signers");
+    }
+  }
+  std::vector<uint64_t> off(n);
+  std::vector<uint32_t> len(n);
+  size_t total = 0;
+  for (size_t i = 0; i < n; i++) {
+    off[i] = total;
+    len[i] = (uint32_t)requests[i].hashLen;
+    total += len[i];
+  }
+  std::vector<uint8_t> blob(total ? total : 1), out(37 * n);
+  for (size_t i = 0; i < n; i++) std::memcpy(blob.data() + off[i], requests[i].hash, len[i]);
+  check(cbft_bls_sign_batch(engine_->ctx(), signer_table_, nullptr, blob.data(), off.data(), len.data(), n, out.data()),
+        "cbft_bls_sign_batch");
+  for (size_t i = 0; i < n; i++) std::memcpy(requests[i].out, out.data() + 37 * i, 37);
+}
+
 }  // namespace Hip
 }  // namespace BLS

@@ -92,6 +92,9 @@ void cbft_close(cbft_ctx* ctx);
  *                         default CBFT_SIGN_GPU_MIN_DEFAULT in hip_crypto.hpp)
  *   CBFT_RSA_SIGN_GPU_MIN smallest HipRSASigner::signBatch that signs on the GPU (host layer;
  *                         default CBFT_RSA_SIGN_GPU_MIN_DEFAULT in hip_crypto.hpp)
+ *   CBFT_BLS_SIGN_BATCH_MIN smallest BlsThresholdSigner::signBatch that signs in one batch call
+ *                         instead of a loop of cbft_bls_sign (host layer; default
+ *                         CBFT_BLS_SIGN_BATCH_MIN_DEFAULT in threshsign/bls_hip.hpp)
  * Geometry and scheduling switches that tests exercise on purpose (both ladder layouts, other B
  * comb radices, the three-kernel path at small sizes, ...) are per-context options, set after
  * cbft_open and before the first batch that should use them; a multi-GPU context applies them
@@ -427,6 +430,34 @@ int cbft_bls_public_key(cbft_ctx* ctx, const uint8_t* sk32, uint8_t* out65);
 /* Sign a share: out37 = 4-byte big-endian id || sk * g1_map(msg) compressed, sk = 32 bytes
  * big-endian (< r) (IThresholdSigner::signData; BlsThresholdSigner.cpp:32-47). */
 int cbft_bls_sign(cbft_ctx* ctx, const uint8_t* sk32, uint32_t id, const uint8_t* msg, uint32_t len, uint8_t* out37);
+
+/* ---- Batched share signing: the batch form of cbft_bls_sign for the shares of many sequence
+ * numbers in flight (SignedShareBase::create, PartialCommitProofMsg), one message per GPU lane,
+ * constant time in the scalar (csrc/bls_sign_batch.h).  Every share is byte for byte what
+ * cbft_bls_sign gives for the same scalar, id and message (BLS shares are deterministic).
+ *
+ * Load a signer table: sk32 = nkeys x 32 bytes big-endian scalars, reduced and checked as
+ * cbft_bls_sign does (CBFT_EINVAL for a scalar that is 0 mod r); ids = nkeys share ids, each in
+ * [1, 2048] (else CBFT_EINVAL).  On a multi-GPU context the table lives on the lowest device. */
+int cbft_bls_load_signers(cbft_ctx* ctx, const uint8_t* sk32, const uint32_t* ids, uint32_t nkeys,
+                          uint32_t* out_signer_table_id);
+/* out65: nkeys x 65 bytes, the signers' share verification keys vk = sk * g2 compressed */
+int cbft_bls_signer_public_keys(cbft_ctx* ctx, uint32_t signer_table_id, uint8_t* out65);
+/* Clears the table's secrets and the signing scratch on the device.  CBFT_EINVAL for an unknown
+ * (or already unloaded) id. */
+int cbft_bls_unload_signers(cbft_ctx* ctx, uint32_t signer_table_id);
+/* Sign n messages (host arrays): message i = msg_blob[msg_off[i] .. + msg_len[i]) under signer
+ * signer_idx[i] (nullptr: all under signer 0); out37 = n x 37 bytes (id || sigma).  Blocking.
+ * signer_idx[i] >= nkeys or msg_len[i] > 0xFFFFFF00 is CBFT_EINVAL before anything is launched,
+ * out37 untouched.  n = 0 is CBFT_OK. */
+int cbft_bls_sign_batch(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t* signer_idx, const uint8_t* msg_blob,
+                        const uint64_t* msg_off, const uint32_t* msg_len, size_t n, uint8_t* out37);
+/* Device-resident form: message i at d_msg + i * msg_len, shares to d_out37 (n x 37 bytes),
+ * asynchronous on `stream` (nullptr = the context's own stream).  An out-of-range d_signer_idx
+ * entry gives 37 zero bytes.  Calls on different streams share the batch scratch and are ordered
+ * by the library.  Single-GPU contexts only. */
+int cbft_bls_sign_fixed_device(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t* d_signer_idx,
+                               const uint8_t* d_msg, uint32_t msg_len, size_t n, uint8_t* d_out37, void* stream);
 
 #ifdef __cplusplus
 }
