@@ -12,8 +12,8 @@ ORACLE_LIB := oracle/libcbft_oracle.so
 # host SIMD emulation of the same source is exact).  Costs one v_mov_dpp per move.
 ROWFLAGS := -mllvm -amdgpu-dpp-combine=false
 
-.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim sanitize selftest
-all: lib oracle cpu host shim fe_row_shim bls_sign_shim selftest
+.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim sha512_shim sanitize selftest
+all: lib oracle cpu host shim fe_row_shim bls_sign_shim sha512_shim selftest
 
 lib: $(LIB)
 
@@ -131,6 +131,16 @@ FE_ROW_SHIM := tests/cpp/libfe_row_shim.so
 fe_row_shim: $(FE_ROW_SHIM)
 $(FE_ROW_SHIM): tests/cpp/fe_row_shim.cpp tests/cpp/row_emu.h $(CSRC)/fe25519_row.h $(CSRC)/row_lanes.h
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -Itests/cpp -o $@ $<
+
+# host build of the fixed-length SHA-512 front end (sha512.h) for tests/test_sha512_fixed_cpu.py, and
+# the same source as a stand-alone program under ASan + UBSan (run by that test, never loaded into python)
+SHA512_SHIM := tests/cpp/libsha512_shim.so
+SHA512_SHIM_SAN := tests/cpp/sha512_shim_san
+sha512_shim: $(SHA512_SHIM) $(SHA512_SHIM_SAN)
+$(SHA512_SHIM): tests/cpp/sha512_shim.cpp $(CSRC)/sha512.h
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $<
+$(SHA512_SHIM_SAN): tests/cpp/sha512_shim.cpp $(CSRC)/sha512.h
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DSHA512_SHIM_MAIN -I$(CSRC) -o $@ $<
 
 # Host-layer sanitizer builds (host code only: the HIP library itself is not instrumented).
 # ASan+UBSan and TSan variants of the C++ host library and its tests; run on a GPU box with

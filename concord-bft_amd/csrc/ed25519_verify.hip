@@ -223,6 +223,13 @@ __device__ __forceinline__ bool unit_aok(const Ed25519Batch& b, const uint8_t* a
 
 // h = SHA-512(R||A||M) mod L of signature i (hw, 8 LE words) and its flag (S < L, key index in
 // range, length supported): K1's per-signature work, also run by the fused small-batch kernel.
+//
+// FIXED_ALIGNED: the batch has one message length for all (no msg_off), a multiple of 4 that is
+// at most CBFT_MAX_MSG_LEN, and a 4-byte aligned blob (cbft_ed25519_launch_verify checks this on the
+// host).  Length, block count and the place of the 0x80 marker are then scalars: the block loop
+// branches on them and the per-lane work in front of the rounds is the loads and the byte swaps
+// (sha512_fixed_window); the general path's clamped indices, byte shifts and masks are not built.
+template <bool FIXED_ALIGNED = false>
 __device__ __forceinline__ void ed25519_hash_sig(const Ed25519Batch& b, size_t i, uint32_t* hw, bool& flag) {
   const uint32_t key = batch_unit(b, i);
   const bool key_ok = !b.key_idx || b.key_idx[i] < b.nkeys;
@@ -230,6 +237,13 @@ __device__ __forceinline__ void ed25519_hash_sig(const Ed25519Batch& b, size_t i
   load_words8(Aw, b.key_idx ? b.keys.pk(key) : b.pk + (size_t)key * 32);
   load_words8(Rw, b.sig + i * 64);
   load_words8(Sw, b.sig + i * 64 + 32);
+  if constexpr (FIXED_ALIGNED) {
+    uint32_t dig[16];
+    sha512_ram_fixed(dig, Rw, Aw, reinterpret_cast<const uint32_t*>(b.msg + i * (size_t)b.fixed_len), b.fixed_len);
+    sc_reduce512(hw, dig);
+    flag = sc_is_canonical(Sw) && key_ok;
+    return;
+  }
   const uint8_t* m = b.msg_off ? b.msg + b.msg_off[i] : b.msg + i * (size_t)b.fixed_len;
   uint32_t len = b.msg_off ? b.msg_len[i] : b.fixed_len;
   const bool len_ok = len <= CBFT_MAX_MSG_LEN;
@@ -432,15 +446,18 @@ __global__ void __launch_bounds__(256) ed25519_bucket_scatter_kernel(const Ed255
 
 // perm: the block-count order (nullable); uniform: its flag word (perm unused when set);
 // nshort (nullable): positions from *nshort on are ed25519_hash_long_kernel's.
+// FIXED_ALIGNED (see ed25519_hash_sig): such a batch is never sorted, so perm, uniform and nshort
+// are null and not read.
+template <bool FIXED_ALIGNED>
 __global__ void __launch_bounds__(CBFT_VERIFY_BLOCK) ed25519_hash_kernel(const Ed25519Batch b, const uint32_t* perm,
                                                                           const uint32_t* uniform, const uint32_t* nshort,
                                                                           uint32_t* h_soa, uint8_t* flags) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= b.n || (nshort && g >= *nshort)) return;
-  const size_t i = perm && !*uniform ? (size_t)perm[g] : g;
+  if (g >= b.n || (!FIXED_ALIGNED && nshort && g >= *nshort)) return;
+  const size_t i = !FIXED_ALIGNED && perm && !*uniform ? (size_t)perm[g] : g;
   uint32_t hw[8];
   bool flag;
-  ed25519_hash_sig(b, i, hw, flag);
+  ed25519_hash_sig<FIXED_ALIGNED>(b, i, hw, flag);
 #pragma unroll
   for (int k = 0; k < 8; k++) h_soa[k * b.n + i] = hw[k];
   flags[i] = flag ? 1 : 0;
@@ -1758,8 +1775,15 @@ hipError_t cbft_ed25519_launch_verify(const Ed25519Batch& b, const Ed25519Work& 
                        (const uint32_t*)w.perm, uniform_w, nshort_w, w.h_soa, w.flags);
     if ((e = hipEventRecord(w.join_ev, w.aux)) != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(ed25519_hash_kernel, grid, block, 0, stream, b, sorted ? (const uint32_t*)w.perm : nullptr,
-                     uniform_w, nshort_w, w.h_soa, w.flags);
+  // one length for all, whole dwords at dword-aligned addresses: the fixed-length front end
+  const bool fixed_aligned = !b.msg_off && b.fixed_len % 4u == 0 && b.fixed_len <= CBFT_MAX_MSG_LEN &&
+                             reinterpret_cast<uintptr_t>(b.msg) % 4u == 0;
+  if (fixed_aligned)
+    hipLaunchKernelGGL(ed25519_hash_kernel<true>, grid, block, 0, stream, b, (const uint32_t*)nullptr,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, w.h_soa, w.flags);
+  else
+    hipLaunchKernelGGL(ed25519_hash_kernel<false>, grid, block, 0, stream, b, sorted ? (const uint32_t*)w.perm : nullptr,
+                       uniform_w, nshort_w, w.h_soa, w.flags);
   // the next batch's hash may start behind this batch's short hashes while the long tail still
   // runs on the aux stream (hash_early), or only after the whole hash stage
   if (order && order->hash_early && (e = hipEventRecord(order->done[0], stream)) != hipSuccess) return e;
