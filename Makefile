@@ -63,10 +63,17 @@ $(CSRC)/bls_sign_batch.o: $(CSRC)/bls_sign_batch.hip $(CSRC)/bls_sign_batch.h $(
 $(CSRC)/cbft_bls_sign.o: $(CSRC)/cbft_bls_sign.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/bls_sign_batch.h $(CSRC)/bls_kernels.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# BLS verification in batches over many messages: its own objects (the other BLS kernels are not touched)
+$(CSRC)/bls_verify_batch.o: $(CSRC)/bls_verify_batch.hip $(CSRC)/bls_verify_batch.h $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
+	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -c $< -o $@
+
+$(CSRC)/cbft_bls_verify_batch.o: $(CSRC)/cbft_bls_verify_batch.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/bls_verify_batch.h $(CSRC)/bls_kernels.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(CSRC)/cbft_internal.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h include/cbft_hipcrypto.h $(CSRC)/bls_kernels.h $(CSRC)/rsa_sign.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o
+$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle: $(ORACLE_LIB)
@@ -92,7 +99,7 @@ HOST_SRC := $(HOST_DIR)/src/hip_ed25519.cpp $(HOST_DIR)/src/hip_rsa.cpp $(HOST_D
 MIRROR_SRC := $(wildcard $(HOST_DIR)/ref_mirror/src/*.cpp)
 HOST_INC := -Iinclude -I$(HOST_DIR)/include -I$(HOST_DIR)/ref_mirror/include -DCBFT_WITH_CLIENT_KEYS_MAP
 HOST_HDRS := $(wildcard $(HOST_DIR)/include/*.hpp $(HOST_DIR)/include/threshsign/*.hpp $(HOST_DIR)/ref_mirror/include/*.hpp $(HOST_DIR)/ref_mirror/include/threshsign/*.h)
-host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tools/host_bench
+host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tools/host_bench
 $(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB)
 	g++ -O2 -std=c++17 -fPIC -shared -Wall $(HOST_INC) -o $@ $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN'
 tests/cpp/test_host: tests/cpp/test_host.cpp $(HOST_LIB)
@@ -105,6 +112,9 @@ tests/cpp/test_rsa_sign_host: tests/cpp/test_rsa_sign_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_bls_sign_host: tests/cpp/test_bls_sign_host.cpp $(HOST_LIB)
+	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+tests/cpp/test_bls_verify_host: tests/cpp/test_bls_verify_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_bls_host: tests/cpp/test_bls_host.cpp $(HOST_LIB)
@@ -154,6 +164,7 @@ sanitize: $(LIB) $(MIRROR_SRC) $(HOST_SRC)
 	  g++ -O1 -g -fno-omit-frame-pointer -fsanitize=$$s -std=c++17 -DCONCORD_BFT_TESTING $(HOST_INC) -o $(SAN_DIR)/test_host_$$t tests/cpp/test_host.cpp -L$(SAN_DIR) -lcbft_host_$$t -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../../concord-bft_amd' && \
 	  g++ -O1 -g -fno-omit-frame-pointer -fsanitize=$$s -std=c++17 $(HOST_INC) -o $(SAN_DIR)/test_sign_host_$$t tests/cpp/test_sign_host.cpp -L$(SAN_DIR) -lcbft_host_$$t -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../../concord-bft_amd' && \
 	  g++ -O1 -g -fno-omit-frame-pointer -fsanitize=$$s -std=c++17 $(HOST_INC) -o $(SAN_DIR)/test_bls_sign_host_$$t tests/cpp/test_bls_sign_host.cpp -L$(SAN_DIR) -lcbft_host_$$t -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../../concord-bft_amd' && \
+	  g++ -O1 -g -fno-omit-frame-pointer -fsanitize=$$s -std=c++17 $(HOST_INC) -o $(SAN_DIR)/test_bls_verify_host_$$t tests/cpp/test_bls_verify_host.cpp -L$(SAN_DIR) -lcbft_host_$$t -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../../concord-bft_amd' && \
 	  g++ -O1 -g -fno-omit-frame-pointer -fsanitize=$$s -std=c++17 $(HOST_INC) -o $(SAN_DIR)/test_bls_host_$$t tests/cpp/test_bls_host.cpp -L$(SAN_DIR) -lcbft_host_$$t -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN' -Wl,-rpath,'$$ORIGIN/../../../concord-bft_amd' || exit 1; \
 	done
 
@@ -172,7 +183,8 @@ SELFTEST := tests/hip/libinv_selftest.so
 SIGN_SELFTEST := tests/hip/libsign_selftest.so
 RSA_SIGN_SELFTEST := tests/hip/librsa_sign_selftest.so
 BLS_SIGN_SELFTEST := tests/hip/libbls_sign_selftest.so
-selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST)
+BLS_VERIFY_SELFTEST := tests/hip/libbls_verify_selftest.so
+selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST)
 $(SELFTEST): tests/hip/inv_selftest.hip $(CSRC)/safegcd30.h
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 # test-only device harness of the signing comb and sc_muladd (tests/test_ed25519_sign_gpu.py)
@@ -185,3 +197,7 @@ $(RSA_SIGN_SELFTEST): tests/hip/rsa_sign_selftest.hip $(CSRC)/rsa_sign.h $(CSRC)
 # kernels beside their rejected variants (tests/test_bls_sign_gpu.py, tools/bls_sign_bench.py)
 $(BLS_SIGN_SELFTEST): tests/hip/bls_sign_selftest.hip $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
+# test-only device harness of the batched BLS verification: the product kernels timed stage by stage
+# (tools/bls_verify_bench.py)
+$(BLS_VERIFY_SELFTEST): tests/hip/bls_verify_selftest.hip $(CSRC)/bls_verify_batch.hip $(CSRC)/bls_verify_batch.h $(CSRC)/bls_sign_batch.h $(BLS_DEPS) $(LIB)
+	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -shared -o $@ $< -Lconcord-bft_amd -lcbft_hipcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'

@@ -135,6 +135,12 @@ ABI = [
     ("cbft_bls_sign_fixed_device", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t,
       ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_bls_verify_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    ("cbft_bls_verify_fixed_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
+      ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_bls_combine_partial", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
       ctypes.c_void_p]),
@@ -657,6 +663,34 @@ class Context:
         _check(self.lib.cbft_bls_sign_fixed_device(
             self.handle, tid, ctypes.c_void_p(d_signer_idx), ctypes.c_void_p(d_msg), msg_len, n,
             ctypes.c_void_p(d_out37), ctypes.c_void_p(stream)), "cbft_bls_sign_fixed_device")
+
+    def bls_verify_batch(self, kid: int, sigs: Sequence[bytes], msgs: Sequence[bytes], key_idx=None,
+                         msg_of=None) -> np.ndarray:
+        """Verdicts (n,) bool of n independent checks: sigs[i] (33 bytes) on msgs[msg_of[i]] (None:
+        msgs[i], needs len(msgs) == len(sigs)) under key slot key_idx[i] of the key set (0 = the group
+        PK, i = vk_i; None: all under slot 0)."""
+        n, m = len(sigs), len(msgs)
+        assert all(len(s) == 33 for s in sigs)
+        blob, offs, lens = pack_messages(msgs)
+        sig = np.frombuffer(b"".join(sigs), dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+        kidx = None if key_idx is None else np.ascontiguousarray(np.asarray(key_idx, dtype=np.uint32))
+        mof = None if msg_of is None else np.ascontiguousarray(np.asarray(msg_of, dtype=np.uint32))
+        assert (kidx is None or kidx.shape[0] == n) and (mof is None or mof.shape[0] == n)
+        out = np.zeros(max(1, (n + 7) // 8), dtype=np.uint8)
+        _check(self.lib.cbft_bls_verify_batch(self.handle, kid, None if kidx is None else _ptr(kidx), _ptr(sig),
+                                              _ptr(blob), _ptr(offs), _ptr(lens), m,
+                                              None if mof is None else _ptr(mof), n, _ptr(out)),
+               "cbft_bls_verify_batch")
+        return bitmap_to_bools(out.tobytes(), n)
+
+    def bls_verify_fixed_device(self, kid: int, d_key_idx: int, d_sig33: int, d_msg: int, msg_len: int, m: int,
+                                d_msg_of: int, n: int, d_valid: int, stream: int = 0):
+        """Fixed-length messages (message j at d_msg + j * msg_len), verdict bytes to d_valid; raw device
+        addresses (0 for d_key_idx: all under slot 0; 0 for d_msg_of: item i signs message i)."""
+        _check(self.lib.cbft_bls_verify_fixed_device(
+            self.handle, kid, ctypes.c_void_p(d_key_idx), ctypes.c_void_p(d_sig33), ctypes.c_void_p(d_msg), msg_len, m,
+            ctypes.c_void_p(d_msg_of), n, ctypes.c_void_p(d_valid), ctypes.c_void_p(stream)),
+            "cbft_bls_verify_fixed_device")
 
     def bls_public_key(self, sk: int) -> bytes:
         """sk * g2, 65 compressed bytes (the signer's share verification key)."""

@@ -274,6 +274,11 @@ struct cbft_ctx {
   DevBuf blss_in, blss_out;          // packed inputs / shares of a host-array batch
   hipEvent_t blss_done = nullptr;    // orders reuse of the scratch across streams
   bool blss_used = false;
+  // BLS verification in batches (cbft_bls_verify_batch.cpp)
+  DevBuf blsv_scratch;               // hash points, decoded signatures, gate flags
+  DevBuf blsv_in, blsv_out;          // packed inputs / verdict bytes of a host-array batch
+  hipEvent_t blsv_done = nullptr;    // orders reuse of the scratch across streams
+  bool blsv_used = false;
   DevBuf bls_gen_lines, bls_msg, bls_H, bls_shares, bls_valid, bls_sig, bls_ids, bls_use, bls_lambda,
       bls_partial, bls_out, bls_ms_ok, bls_bitmap, bls_inv, bls_first, bls_flag, bls_g2tmp;
   DevBuf bls_aff;      // the last combine's signature as an affine point (BLS_SIG_WORDS)
@@ -287,6 +292,7 @@ cbft_ctx* cbft_dev0(cbft_ctx* c);
 void cbft_sign_release(cbft_ctx* c);
 void cbft_rsa_sign_release(cbft_ctx* c);
 void cbft_bls_sign_release(cbft_ctx* c);
+void cbft_bls_verify_batch_release(cbft_ctx* c);
 // 32-byte big-endian BLS scalar -> 8 little-endian words reduced mod r, as cbft_bls_sign takes it;
 // false for 0 (mod r)
 bool cbft_bls_scalar_words(uint32_t* w, const uint8_t* sk32);

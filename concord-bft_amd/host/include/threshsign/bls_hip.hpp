@@ -61,6 +61,33 @@ class BlsSecretKey : public IShareSecretKey {
   std::array<uint8_t, 32> be_{};
 };
 
+// One check of BlsThresholdVerifier::verifyBatch.  signer == 0: sig is a 33-byte combined signature,
+// ok = what verify(msg, msgLen, sig, sigLen) gives.  signer >= 1: sig is that signer's share, 37 bytes
+// (id || point, the id must be the signer's) or the 33-byte point alone, ok = what an accumulator's
+// share check gives (false for a signer outside [1, numSigners] or any other length).
+struct BlsVerifyRequest {
+  const char* msg;
+  int msgLen;
+  const char* sig;
+  int sigLen;
+  ShareID signer;
+  bool ok;
+};
+
+// What verifyBatch hands to ONE cbft_bls_verify_batch call: the requests that pass the length and id
+// checks (item j is request item[j]), identical messages stored once (msgOf).  Built without the GPU.
+struct BlsVerifyPlan {
+  std::vector<uint32_t> item, keyIdx, msgOf, msgLen;
+  std::vector<uint64_t> msgOff;
+  std::vector<uint8_t> sig33, blob;
+};
+
+// Smallest BlsThresholdVerifier::verifyBatch that runs as ONE cbft_bls_verify_batch call
+// ($CBFT_BLS_VERIFY_BATCH_MIN overrides); smaller batches loop the lone calls (cbft_bls_verify,
+// cbft_bls_verify_shares).  The measured crossover of one batch call against n lone cbft_bls_verify
+// calls, host arrays in to verdicts out.
+#define CBFT_BLS_VERIFY_BATCH_MIN_DEFAULT 2
+
 class BlsThresholdVerifier : public IThresholdVerifier {
  public:
   // vkHex: numSigners share verification keys vk_1..vk_n (the reference's vector has a dummy
@@ -71,6 +98,13 @@ class BlsThresholdVerifier : public IThresholdVerifier {
 
   IThresholdAccumulator* newAccumulator(bool withShareVerification) const override;
   bool verify(const char* msg, int msgLen, const char* sig, int sigLen) const override;
+  // The batch form of verify and of the accumulators' share check for the certificates and shares of
+  // many sequence numbers: every request's ok is set.  batchMin() requests or more run as one
+  // cbft_bls_verify_batch call, fewer as lone calls; the verdicts are the same.
+  virtual void verifyBatch(std::vector<BlsVerifyRequest>& requests) const;
+  static size_t batchMin();
+  // the requests that need a pairing, packed for one call; the others get ok = false here
+  static void planBatch(std::vector<BlsVerifyRequest>& requests, NumSharesType numSigners, BlsVerifyPlan& plan);
   int requiredLengthForSignedData() const override { return 33; }
   const IPublicKey& getPublicKey() const override { return pk_; }
   const IShareVerificationKey& getShareVerificationKey(ShareID signer) const override;
@@ -97,6 +131,10 @@ class BlsMultisigVerifier : public BlsThresholdVerifier {
   int requiredLengthForSignedData() const override;
   // throws std::runtime_error on a wrong-size k-of-n signature (BlsMultisigVerifier.cpp:77)
   bool verify(const char* msg, int msgLen, const char* sig, int sigLen) const override;
+  // n-of-n: 33-byte signatures go through the batch under the summed key.  k-of-n: a signature carries
+  // its signer bitmap and its own key sum, so signer == 0 requests fall back to verify() one by one
+  // (ok = false instead of verify()'s exception for a wrong size); shares still run as one batch.
+  void verifyBatch(std::vector<BlsVerifyRequest>& requests) const override;
 };
 
 // Accumulator state machine of ThresholdAccumulatorBase (pending / valid / invalid shares).

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <mutex>
 #include <stdexcept>
+#include <unordered_map>
 
 #include "cbft_hipcrypto.h"
 
@@ -128,6 +129,84 @@ bool BlsThresholdVerifier::verify(const char* msg, int msgLen, const char* sig, 
   return ok != 0;
 }
 
+static void putRecord(std::vector<uint8_t>& out, ShareID id, const uint8_t* s33);
+
+size_t BlsThresholdVerifier::batchMin() {
+  static const size_t v = [] {
+    const char* e = std::getenv("CBFT_BLS_VERIFY_BATCH_MIN");
+    const long long x = e ? std::atoll(e) : 0;
+    return x > 0 ? (size_t)x : (size_t)CBFT_BLS_VERIFY_BATCH_MIN_DEFAULT;
+  }();
+  return v;
+}
+
+void BlsThresholdVerifier::planBatch(std::vector<BlsVerifyRequest>& requests, NumSharesType numSigners,
+                                     BlsVerifyPlan& plan) {
+  plan = BlsVerifyPlan();
+  std::unordered_map<std::string, uint32_t> seen;  // message bytes -> its index in the plan
+  for (size_t i = 0; i < requests.size(); i++) {
+    BlsVerifyRequest& r = requests[i];
+    r.ok = false;
+    if (!r.msg || r.msgLen < 0 || !r.sig) continue;
+    const uint8_t* s = reinterpret_cast<const uint8_t*>(r.sig);
+    if (r.signer == 0) {
+      if (r.sigLen != 33) continue;  // verify(): false
+    } else {
+      if (r.signer < 1 || r.signer > numSigners) continue;
+      if (r.sigLen == 37) {
+        const uint32_t id = ((uint32_t)s[0] << 24) | ((uint32_t)s[1] << 16) | ((uint32_t)s[2] << 8) | s[3];
+        if (id != (uint32_t)r.signer) continue;  // another signer's record
+        s += 4;
+      } else if (r.sigLen != 33) {
+        continue;  // add(): a point that never decodes
+      }
+    }
+    std::string key(r.msg, (size_t)r.msgLen);
+    auto it = seen.find(key);
+    if (it == seen.end()) {
+      it = seen.emplace(std::move(key), (uint32_t)plan.msgLen.size()).first;
+      plan.msgOff.push_back(plan.blob.size());
+      plan.msgLen.push_back((uint32_t)r.msgLen);
+      plan.blob.insert(plan.blob.end(), r.msg, r.msg + r.msgLen);
+    }
+    plan.item.push_back((uint32_t)i);
+    plan.keyIdx.push_back((uint32_t)r.signer);
+    plan.msgOf.push_back(it->second);
+    plan.sig33.insert(plan.sig33.end(), s, s + 33);
+  }
+}
+
+void BlsThresholdVerifier::verifyBatch(std::vector<BlsVerifyRequest>& requests) const {
+  BlsVerifyPlan p;
+  planBatch(requests, num_, p);
+  const size_t n = p.item.size();
+  if (n == 0) return;
+  if (requests.size() < batchMin()) {
+    for (size_t j = 0; j < n; j++) {
+      BlsVerifyRequest& r = requests[p.item[j]];
+      const uint8_t* s33 = &p.sig33[33 * j];
+      if (r.signer == 0) {
+        r.ok = verify(r.msg, r.msgLen, reinterpret_cast<const char*>(s33), 33);
+        continue;
+      }
+      std::vector<uint8_t> rec;
+      putRecord(rec, r.signer, s33);
+      uint8_t bit = 0;
+      check(cbft_bls_verify_shares(engine_->ctx(), keyset_, reinterpret_cast<const uint8_t*>(r.msg), (uint32_t)r.msgLen,
+                                   rec.data(), 1, &bit),
+            "cbft_bls_verify_shares");
+      r.ok = (bit & 1) != 0;
+    }
+    return;
+  }
+  if (p.blob.empty()) p.blob.push_back(0);
+  std::vector<uint8_t> bits((n + 7) / 8);
+  check(cbft_bls_verify_batch(engine_->ctx(), keyset_, p.keyIdx.data(), p.sig33.data(), p.blob.data(), p.msgOff.data(),
+                              p.msgLen.data(), p.msgLen.size(), p.msgOf.data(), n, bits.data()),
+        "cbft_bls_verify_batch");
+  for (size_t j = 0; j < n; j++) requests[p.item[j]].ok = ((bits[j >> 3] >> (j & 7)) & 1) != 0;
+}
+
 static std::vector<uint8_t> allSigners(NumSharesType n) {
   VectorOfShares v;
   for (ShareID i = 1; i <= n; i++) v.add(i);
@@ -176,6 +255,24 @@ bool BlsMultisigVerifier::verify(const char* msg, int msgLen, const char* sig, i
                                  reinterpret_cast<const uint8_t*>(sig) + 33, &ok),
         "cbft_bls_verify_multisig");
   return ok != 0;
+}
+
+void BlsMultisigVerifier::verifyBatch(std::vector<BlsVerifyRequest>& requests) const {
+  if (req_ == num_) return BlsThresholdVerifier::verifyBatch(requests);
+  // the shares as one batch; each k-of-n signature under its own key sum, by verify()
+  std::vector<BlsVerifyRequest> shares;
+  std::vector<size_t> at;
+  for (size_t i = 0; i < requests.size(); i++) {
+    BlsVerifyRequest& r = requests[i];
+    if (r.signer != 0) {
+      shares.push_back(r);
+      at.push_back(i);
+    } else {
+      r.ok = r.sigLen == requiredLengthForSignedData() && verify(r.msg, r.msgLen, r.sig, r.sigLen);
+    }
+  }
+  BlsThresholdVerifier::verifyBatch(shares);
+  for (size_t j = 0; j < at.size(); j++) requests[at[j]].ok = shares[j].ok;
 }
 
 // ------------------------------------------------------------------------------ accumulators

@@ -459,6 +459,32 @@ int cbft_bls_sign_batch(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t*
 int cbft_bls_sign_fixed_device(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t* d_signer_idx,
                                const uint8_t* d_msg, uint32_t msg_len, size_t n, uint8_t* d_out37, void* stream);
 
+/* ---- Batched verification over many messages: n independent pairing checks, each with its own
+ * message and its own key slot of the key set (key_idx[i] = 0: the group PK, i >= 1: vk_i; nullptr:
+ * all under slot 0).  Item i signs message msg_of[i] of the m messages (nullptr: message i, which
+ * needs m == n), so the shares of one digest hash it once.  Item i is valid iff its key decoded
+ * (cbft_bls_key_status), sig33[i] decodes and e(g1_map(msg), key) == e(sigma, g2): for slot 0 the
+ * verdict of cbft_bls_verify on that item alone, for slot id >= 1 the verdict of
+ * cbft_bls_verify_shares on the lone share be32(id) || sig33[i].  Verdicts are exact, per item (no
+ * random linear combination).
+ *
+ * Host arrays: message j = msg_blob[msg_off[j] .. + msg_len[j]); bit i of valid_bitmap (ceil(n/8)
+ * bytes, LSB first, trailing bits 0).  Blocking.  CBFT_EINVAL before anything is launched, bitmap
+ * untouched: unknown key set, key_idx[i] > n_keys, msg_of[i] >= m, msg_len[j] > 0xFFFFFF00, or
+ * msg_of == nullptr with m != n.  n = 0 is CBFT_OK.  Up to 2^26 items per call (CBFT_E2BIG).  On a
+ * multi-GPU context each device verifies a contiguous slice of the items and hashes only the
+ * messages that slice names. */
+int cbft_bls_verify_batch(cbft_ctx* ctx, uint32_t keyset, const uint32_t* key_idx, const uint8_t* sig33,
+                          const uint8_t* msg_blob, const uint64_t* msg_off, const uint32_t* msg_len, size_t m,
+                          const uint32_t* msg_of, size_t n, uint8_t* valid_bitmap);
+/* Device-resident form: message j at d_msg + j * msg_len, verdicts to d_valid (n bytes, 0 / 1),
+ * asynchronous on `stream` (nullptr = the context's own stream).  An out-of-range d_key_idx or
+ * d_msg_of entry gives verdict 0.  Calls on different streams share the batch scratch and are ordered
+ * by the library.  Single-GPU contexts only. */
+int cbft_bls_verify_fixed_device(cbft_ctx* ctx, uint32_t keyset, const uint32_t* d_key_idx, const uint8_t* d_sig33,
+                                 const uint8_t* d_msg, uint32_t msg_len, size_t m, const uint32_t* d_msg_of, size_t n,
+                                 uint8_t* d_valid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
