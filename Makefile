@@ -12,8 +12,8 @@ ORACLE_LIB := oracle/libcbft_oracle.so
 # host SIMD emulation of the same source is exact).  Costs one v_mov_dpp per move.
 ROWFLAGS := -mllvm -amdgpu-dpp-combine=false
 
-.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim sha512_shim sanitize selftest
-all: lib oracle cpu host shim fe_row_shim bls_sign_shim sha512_shim selftest
+.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim sanitize selftest
+all: lib oracle cpu host shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim selftest
 
 lib: $(LIB)
 
@@ -70,10 +70,18 @@ $(CSRC)/bls_verify_batch.o: $(CSRC)/bls_verify_batch.hip $(CSRC)/bls_verify_batc
 $(CSRC)/cbft_bls_verify_batch.o: $(CSRC)/cbft_bls_verify_batch.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/bls_verify_batch.h $(CSRC)/bls_kernels.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# ECDSA secp256k1 verification: its own objects (no other kernel is touched)
+ECDSA_DEPS := $(CSRC)/ecdsa_verify.h $(CSRC)/fe_secp256k1.h $(CSRC)/sc_secp256k1.h $(CSRC)/ge_secp256k1.h $(CSRC)/safegcd30.h $(CSRC)/sha256.h
+$(CSRC)/ecdsa_verify.o: $(CSRC)/ecdsa_verify.hip $(ECDSA_DEPS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/cbft_ecdsa.o: $(CSRC)/cbft_ecdsa.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(ECDSA_DEPS) $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(CSRC)/cbft_internal.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h include/cbft_hipcrypto.h $(CSRC)/bls_kernels.h $(CSRC)/rsa_sign.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o
+$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle: $(ORACLE_LIB)
@@ -88,6 +96,11 @@ CPU_LIB := tools/cpu_baseline/libcbft_cpu_openssl.so
 cpu: $(CPU_LIB)
 $(CPU_LIB): tools/cpu_baseline/openssl_ed25519.c
 	gcc -O2 -std=gnu11 -fPIC -shared -Wall -Wno-deprecated-declarations -o $@ $< -lcrypto -lpthread
+# the ECDSA secp256k1 host baseline of tools/ecdsa_bench.py (threads of ECDSA_do_verify)
+CPU_ECDSA_LIB := tools/cpu_baseline/libcbft_cpu_openssl_ecdsa.so
+cpu: $(CPU_ECDSA_LIB)
+$(CPU_ECDSA_LIB): tools/cpu_baseline/openssl_ecdsa.c
+	gcc -O2 -std=gnu11 -fPIC -shared -Wall -Wno-deprecated-declarations -o $@ $< -lcrypto -lpthread
 
 # C++ plugin layer.  Product sources (concord::hip, BLS::Hip) compile against the reference's own
 # headers in an integration build (tests/test_reference_boundary.py) and here against the
@@ -95,11 +108,11 @@ $(CPU_LIB): tools/cpu_baseline/openssl_ed25519.c
 # Crypto++, RELIC and CMF-generated code that the image does not have).
 HOST_LIB := concord-bft_amd/libcbft_host.so
 HOST_DIR := concord-bft_amd/host
-HOST_SRC := $(HOST_DIR)/src/hip_ed25519.cpp $(HOST_DIR)/src/hip_rsa.cpp $(HOST_DIR)/src/bls_hip.cpp $(HOST_DIR)/src/request_batch.cpp
+HOST_SRC := $(HOST_DIR)/src/hip_ed25519.cpp $(HOST_DIR)/src/hip_rsa.cpp $(HOST_DIR)/src/hip_ecdsa.cpp $(HOST_DIR)/src/bls_hip.cpp $(HOST_DIR)/src/request_batch.cpp
 MIRROR_SRC := $(wildcard $(HOST_DIR)/ref_mirror/src/*.cpp)
 HOST_INC := -Iinclude -I$(HOST_DIR)/include -I$(HOST_DIR)/ref_mirror/include -DCBFT_WITH_CLIENT_KEYS_MAP
 HOST_HDRS := $(wildcard $(HOST_DIR)/include/*.hpp $(HOST_DIR)/include/threshsign/*.hpp $(HOST_DIR)/ref_mirror/include/*.hpp $(HOST_DIR)/ref_mirror/include/threshsign/*.h)
-host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tools/host_bench
+host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_ecdsa_host tools/host_bench
 $(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB)
 	g++ -O2 -std=c++17 -fPIC -shared -Wall $(HOST_INC) -o $@ $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN'
 tests/cpp/test_host: tests/cpp/test_host.cpp $(HOST_LIB)
@@ -116,6 +129,9 @@ tests/cpp/test_bls_sign_host: tests/cpp/test_bls_sign_host.cpp $(HOST_LIB)
 
 tests/cpp/test_bls_verify_host: tests/cpp/test_bls_verify_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+tests/cpp/test_ecdsa_host: tests/cpp/test_ecdsa_host.cpp $(HOST_LIB)
+	g++ -O2 -std=c++17 -Wall -Wno-deprecated-declarations $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_bls_host: tests/cpp/test_bls_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
@@ -151,6 +167,16 @@ $(SHA512_SHIM): tests/cpp/sha512_shim.cpp $(CSRC)/sha512.h
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $<
 $(SHA512_SHIM_SAN): tests/cpp/sha512_shim.cpp $(CSRC)/sha512.h
 	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DSHA512_SHIM_MAIN -I$(CSRC) -o $@ $<
+
+# host build of the ECDSA secp256k1 lane code (ecdsa_verify.h) for tests/test_ecdsa_cpu.py, and the
+# same source as a stand-alone program under ASan + UBSan (run by that test, never loaded into python)
+ECDSA_SHIM := tests/cpp/libecdsa_shim.so
+ECDSA_SHIM_SAN := tests/cpp/ecdsa_shim_san
+ecdsa_shim: $(ECDSA_SHIM) $(ECDSA_SHIM_SAN)
+$(ECDSA_SHIM): tests/cpp/ecdsa_shim.cpp $(ECDSA_DEPS)
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $<
+$(ECDSA_SHIM_SAN): tests/cpp/ecdsa_shim.cpp $(ECDSA_DEPS)
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DECDSA_SHIM_MAIN -I$(CSRC) -o $@ $<
 
 # Host-layer sanitizer builds (host code only: the HIP library itself is not instrumented).
 # ASan+UBSan and TSan variants of the C++ host library and its tests; run on a GPU box with

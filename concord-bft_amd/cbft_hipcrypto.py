@@ -150,6 +150,16 @@ ABI = [
     ("cbft_bls_verify_multisig_partials", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32,
       ctypes.POINTER(ctypes.c_int)]),
+    ("cbft_ecdsa_load_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _u32p]),
+    ("cbft_ecdsa_key_status", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("cbft_ecdsa_unload_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    ("cbft_ecdsa_verify_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p]),
+    ("cbft_ecdsa_verify_batch_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_ecdsa_kernel_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
 ]
 
 # cbft_set_option options (include/cbft_hipcrypto.h, "tuning")
@@ -480,6 +490,52 @@ class Context:
         _check(self.lib.cbft_rsa_kernel_ms(self.handle, ctypes.byref(out)), "cbft_rsa_kernel_ms")
         return out.value
 
+    # ------------------------------------------------------------------ ECDSA secp256k1 / SHA-256
+    def ecdsa_load_keys(self, keys) -> int:
+        """keys: 64-byte public keys (X || Y big-endian), a list of bytes or an (n, 64) uint8 array."""
+        k = _as_rows(keys, 64)
+        buf = k if k.shape[0] else np.zeros((1, 64), np.uint8)
+        tid = ctypes.c_uint32()
+        _check(self.lib.cbft_ecdsa_load_keys(self.handle, _ptr(buf), k.shape[0], ctypes.byref(tid)),
+               "cbft_ecdsa_load_keys")
+        return tid.value
+
+    def ecdsa_unload_keys(self, tid: int):
+        _check(self.lib.cbft_ecdsa_unload_keys(self.handle, tid), "cbft_ecdsa_unload_keys")
+
+    def ecdsa_key_status(self, tid: int, nkeys: int) -> np.ndarray:
+        out = np.zeros(max(1, nkeys), dtype=np.uint8)
+        _check(self.lib.cbft_ecdsa_key_status(self.handle, tid, _ptr(out)), "cbft_ecdsa_key_status")
+        return out[:nkeys].astype(bool)
+
+    def ecdsa_verify(self, tid: int, key_idx, sigs, msgs: Sequence[bytes]) -> bytes:
+        """sigs: 64-byte signatures (r || s big-endian).  Returns the verdict bitmap."""
+        n = len(msgs)
+        kidx = np.ascontiguousarray(np.asarray(key_idx, dtype=np.uint32))
+        s = _as_rows(sigs, 64)
+        assert kidx.shape[0] == n and s.shape[0] == n
+        blob, offs, lens = pack_messages(msgs)
+        out = np.zeros(max(1, (n + 7) // 8), dtype=np.uint8)
+        _check(self.lib.cbft_ecdsa_verify_batch(self.handle, tid, _ptr(kidx), _ptr(s), _ptr(blob), _ptr(offs),
+                                                 _ptr(lens), n, _ptr(out)), "cbft_ecdsa_verify_batch")
+        return out.tobytes()[: (n + 7) // 8]
+
+    def ecdsa_verify_device(self, tid: int, d_key_idx, d_sig, d_msg, d_off, d_len, n: int, d_verdict_words,
+                            stream=0):
+        """Device-resident batch, asynchronous on `stream`.  Arrays: torch tensors on this context's
+        GPU (uint32 indices, uint8 signatures and blob, int64 offsets, int32 lengths, int64 verdict
+        words) or raw device addresses; stream: a torch stream or a raw hipStream_t (0 = the
+        context's own)."""
+        _check(self.lib.cbft_ecdsa_verify_batch_device(
+            self.handle, tid, _dev_ptr(d_key_idx), _dev_ptr(d_sig), _dev_ptr(d_msg), _dev_ptr(d_off),
+            _dev_ptr(d_len), n, _dev_ptr(d_verdict_words),
+            ctypes.c_void_p(getattr(stream, "cuda_stream", stream))), "cbft_ecdsa_verify_batch_device")
+
+    def ecdsa_kernel_ms(self) -> float:
+        out = ctypes.c_float()
+        _check(self.lib.cbft_ecdsa_kernel_ms(self.handle, ctypes.byref(out)), "cbft_ecdsa_kernel_ms")
+        return out.value
+
     # ------------------------------------------------------------------ RSA-2048 signing (CRT)
     def rsa_load_signers(self, keys: Sequence[tuple]) -> int:
         """keys: (p, q, dP, dQ, qInv, e) integer tuples (1,024-bit primes in either order, qInv =
@@ -715,6 +771,11 @@ class Context:
         out = (ctypes.c_float * 3)()
         _check(self.lib.cbft_stage_times_ms(self.handle, out, 3), "cbft_stage_times_ms")
         return {"hash": out[0], "ladder": out[1], "finish": out[2]}
+
+
+def _dev_ptr(x):
+    """A device address from a raw integer or from anything with data_ptr() (a torch tensor)."""
+    return ctypes.c_void_p(x.data_ptr() if hasattr(x, "data_ptr") else x)
 
 
 def _as_rows(x, width: int) -> np.ndarray:

@@ -358,6 +358,7 @@ void cbft_close(cbft_ctx* c) {
   cbft_rsa_sign_release(c);
   cbft_bls_sign_release(c);
   cbft_bls_verify_batch_release(c);
+  cbft_ecdsa_release(c);
   for (auto& kv : c->rsa_tables) kv.second.rec.release();
   for (DevBuf* b : {&c->rsa_scratch, &c->rsa_sig, &c->rsa_kidx}) b->release();
   for (hipEvent_t e : {c->rsa_done, c->rsa_ev[0], c->rsa_ev[1]})

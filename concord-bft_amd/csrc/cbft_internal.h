@@ -147,6 +147,13 @@ struct RsaKeyTable {
   DevBuf rec;
 };
 
+// ECDSA secp256k1 verifier key table: per-key records (window table of affine multiples,
+// validity) built on the GPU at load time (ecdsa_verify.h ECDSA_KEY_WORDS)
+struct EcdsaKeyTable {
+  uint32_t nkeys = 0;
+  DevBuf rec;
+};
+
 // Ed25519 signer table: per-signer records (clamped scalar a, prefix, public key A) derived on
 // the GPU from the seeds at load time (ed25519_sign.h CBFT_SIGNER_WORDS)
 struct SignerTable {
@@ -279,6 +286,15 @@ struct cbft_ctx {
   DevBuf blsv_in, blsv_out;          // packed inputs / verdict bytes of a host-array batch
   hipEvent_t blsv_done = nullptr;    // orders reuse of the scratch across streams
   bool blsv_used = false;
+  // ECDSA secp256k1 verification (cbft_ecdsa.cpp)
+  std::unordered_map<uint32_t, EcdsaKeyTable> ecdsa_tables;
+  uint32_t next_ecdsa_id = 1;
+  DevBuf ecdsa_gtab;                 // G's window table (the record of the key Q = G), built at the first load
+  DevBuf ecdsa_scratch, ecdsa_sig, ecdsa_kidx;  // digests; signatures / indices of a host-array batch
+  hipEvent_t ecdsa_done = nullptr;   // orders reuse of the scratch across streams
+  bool ecdsa_used = false;
+  hipEvent_t ecdsa_ev[2] = {nullptr, nullptr};  // around the last ECDSA batch's kernels when profiling
+  bool ecdsa_ev_valid = false;
   DevBuf bls_gen_lines, bls_msg, bls_H, bls_shares, bls_valid, bls_sig, bls_ids, bls_use, bls_lambda,
       bls_partial, bls_out, bls_ms_ok, bls_bitmap, bls_inv, bls_first, bls_flag, bls_g2tmp;
   DevBuf bls_aff;      // the last combine's signature as an affine point (BLS_SIG_WORDS)
@@ -293,6 +309,7 @@ void cbft_sign_release(cbft_ctx* c);
 void cbft_rsa_sign_release(cbft_ctx* c);
 void cbft_bls_sign_release(cbft_ctx* c);
 void cbft_bls_verify_batch_release(cbft_ctx* c);
+void cbft_ecdsa_release(cbft_ctx* c);
 // 32-byte big-endian BLS scalar -> 8 little-endian words reduced mod r, as cbft_bls_sign takes it;
 // false for 0 (mod r)
 bool cbft_bls_scalar_words(uint32_t* w, const uint8_t* sk32);

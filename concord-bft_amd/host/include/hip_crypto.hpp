@@ -1,7 +1,7 @@
 // GPU-backed implementations of the reference's signature plugin interface
 // (concord::util::crypto::IVerifier / ISigner, util/include/crypto_utils.hpp:41-55) over
 // libcbft_hipcrypto, in namespace concord::hip so that nothing here redefines a reference symbol:
-// this header and hip_verifiers.cpp / hip_rsa.cpp compile against the reference's own
+// this header and hip_verifiers.cpp / hip_rsa.cpp / hip_ecdsa.cpp compile against the reference's own
 // crypto_utils.hpp (tests/test_reference_boundary.py) or, where the reference cannot be built,
 // against the restatement in ref_mirror/include/crypto_utils.hpp.
 //
@@ -11,6 +11,9 @@
 //                                  golden vectors
 //   HipRSAVerifier : IVerifier     RSASS<PKCS1v15, SHA256> with Crypto++ 8.2.0 semantics
 //                                  (util/src/crypto_utils.cpp:101-117), 2048-bit moduli
+//   HipECDSAVerifier : IVerifier   ECDSA / SHA-256 (Crypto++ ECDSA<ECP, SHA256>, crypto_utils.cpp:34-64):
+//                                  secp256k1 keys on the GPU with OpenSSL 3.0.2's verdicts, keys on
+//                                  other curves on the host OpenSSL
 //   EdDSASigner : ISigner          Ed25519 signing: sign() on the host OpenSSL (one signature is
 //                                  latency-bound on any device); signBatch() on the GPU from
 //                                  CBFT_SIGN_GPU_MIN requests up (the pre-processing path signs one
@@ -133,6 +136,53 @@ class HipRSAVerifier : public IVerifier {
   std::string key_str_;
   uint32_t key_index_;
   std::shared_ptr<RsaEngine> engine_;
+};
+
+class EcdsaEngine;  // per-process owner of the cbft_ctx and of the device ECDSA key table
+
+// Smallest number of secp256k1 items in one verifyBatch (or one verify(): 1) that goes to the GPU
+// ($CBFT_ECDSA_GPU_MIN overrides): the measured crossover of one cbft_ecdsa_verify_batch call, host
+// arrays in to bitmap out, against a one-thread loop of OpenSSL ECDSA_do_verify.
+// Below it the items are verified on the host with OpenSSL, whose verdicts the GPU path reproduces.
+#define CBFT_ECDSA_GPU_MIN_DEFAULT 32
+
+// ECDSA / SHA-256 in place of concord::util::crypto::ECDSAVerifier (Crypto++ ECDSA<ECP, SHA256>,
+// util/include/crypto_utils.hpp:57-77).  Signatures are r || s, each as long as the group order
+// (IEEE P1363, what Crypto++ reads and writes).  A secp256k1 key (the reference's default curve)
+// registers with the process's key table and is verified on the GPU from gpuMinBatch() items per
+// call up; a key on any other curve the host OpenSSL knows (KeyExchangeManager generates secp384r1
+// keys) is verified with OpenSSL.
+class HipECDSAVerifier : public IVerifier {
+ public:
+  // X.509 SubjectPublicKeyInfo of an EC key, hex DER or PEM.  Throws std::invalid_argument unless it
+  // parses as an EC public key on a named curve.
+  HipECDSAVerifier(const std::string& str_pub_key, KeyFormat fmt);
+  ~HipECDSAVerifier() override;
+  HipECDSAVerifier(const HipECDSAVerifier&) = delete;
+  HipECDSAVerifier& operator=(const HipECDSAVerifier&) = delete;
+
+  // false for any signature whose length is not signatureLength() (Crypto++ throws for a short
+  // one; verify() here never throws on bad input), otherwise the ECDSA verdict.
+  bool verify(const std::string& data, const std::string& sig) const override;
+  uint32_t signatureLength() const override { return sig_len_; }
+  std::string getPubKey() const override { return key_str_; }
+
+  bool gpuCapable() const { return gpu_capable_; }
+  uint32_t engineKeyIndex() const { return key_index_; }
+  static size_t gpuMinBatch();
+  // Verifies every request whose verifier is a HipECDSAVerifier: the secp256k1 ones in one GPU
+  // batch when there are gpuMinBatch() or more of them, everything else on the host; out[i] =
+  // verdict of reqs[i] (false for other verifier types).
+  static void verifyBatch(const std::vector<VerifyRequest>& reqs, std::vector<bool>& out);
+
+ private:
+  bool verifyHost(const char* data, size_t len, const char* sig, size_t sig_len) const;
+  std::string key_str_;
+  uint32_t sig_len_ = 0;
+  bool gpu_capable_ = false;
+  uint32_t key_index_ = 0;
+  void* pkey_ = nullptr;  // EVP_PKEY* for the host path
+  std::shared_ptr<EcdsaEngine> engine_;
 };
 
 class EdDSASigner : public ISigner {

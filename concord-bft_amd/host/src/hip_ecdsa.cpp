@@ -1,0 +1,279 @@
+// HipECDSAVerifier over libcbft_hipcrypto (see hip_crypto.hpp).
+//
+// Reference: concord::util::crypto::ECDSAVerifier (util/src/crypto_utils.cpp:34-64,231-236):
+// Crypto++ ECDSA<ECP, SHA256>, default curve secp256k1, keyed from hex DER (X509PublicKey) or PEM;
+// its call site is reconfiguration_handler.cpp:332-338.  Key parsing here uses the host OpenSSL
+// (d2i_PUBKEY / PEM_read_bio_PUBKEY); secp256k1 batches of gpuMinBatch() items and more run on the
+// GPU, smaller ones and other curves on the host OpenSSL (the GPU path reproduces its verdicts).
+#include <openssl/bio.h>
+#include <openssl/bn.h>
+#include <openssl/core_names.h>
+#include <openssl/ecdsa.h>
+#include <openssl/evp.h>
+#include <openssl/pem.h>
+
+#include <atomic>
+#include <cstdlib>
+#include <cstring>
+#include <map>
+#include <mutex>
+#include <shared_mutex>
+#include <stdexcept>
+
+#include "cbft_hipcrypto.h"
+#include "hip_crypto.hpp"
+
+namespace concord::hip {
+
+namespace {
+
+EVP_PKEY* parseEcPublicKey(const std::string& s, KeyFormat fmt) {
+  if (fmt == KeyFormat::HexaDecimalStrippedFormat) {
+    std::vector<uint8_t> der;
+    if (!fromHex(s, der) || der.empty()) return nullptr;
+    const unsigned char* p = der.data();
+    return d2i_PUBKEY(nullptr, &p, (long)der.size());
+  }
+  BIO* bio = BIO_new_mem_buf(s.data(), (int)s.size());
+  if (!bio) return nullptr;
+  EVP_PKEY* k = PEM_read_bio_PUBKEY(bio, nullptr, nullptr, nullptr);
+  BIO_free(bio);
+  return k;
+}
+
+[[noreturn]] void fail(const char* what, int rc) {
+  throw std::runtime_error(std::string(what) + ": " + cbft_strerror(rc) + " " + cbft_last_error());
+}
+
+}  // namespace
+
+// Per-process owner of the GPU context and the device ECDSA key table (keys deduplicated, the
+// table rebuilt lazily before the first batch that needs a newly registered key) -- the twin of
+// RsaEngine in hip_rsa.cpp.
+class EcdsaEngine {
+ public:
+  static std::shared_ptr<EcdsaEngine> get() {
+    static std::mutex m;
+    static std::weak_ptr<EcdsaEngine> inst;
+    std::lock_guard<std::mutex> g(m);
+    auto sp = inst.lock();
+    if (!sp) {
+      sp = std::shared_ptr<EcdsaEngine>(new EcdsaEngine());
+      inst = sp;
+    }
+    return sp;
+  }
+  ~EcdsaEngine() {
+    if (ctx_) cbft_close(ctx_);
+  }
+
+  // registration needs no GPU: the context is opened by the first batch
+  uint32_t registerKey(const uint8_t pub[64]) {
+    std::lock_guard<std::mutex> g(mu_);
+    std::string k(reinterpret_cast<const char*>(pub), 64);
+    auto it = index_.find(k);
+    if (it != index_.end()) return it->second;
+    const uint32_t idx = (uint32_t)(pubs_.size() / 64);
+    pubs_.insert(pubs_.end(), pub, pub + 64);
+    index_.emplace(std::move(k), idx);
+    return idx;
+  }
+
+  // one batch of 64-byte signatures; GPU failures become false verdicts and are counted
+  void verifyNoThrow(const std::vector<uint32_t>& kidx, const std::vector<uint8_t>& sig, const std::vector<uint8_t>& msg,
+                     const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, std::vector<uint8_t>& bitmap) {
+    try {
+      verify(kidx, sig, msg, off, len, bitmap);
+    } catch (...) {
+      gpu_errors_++;
+      std::fill(bitmap.begin(), bitmap.end(), 0);
+    }
+  }
+
+ private:
+  static constexpr uint32_t kNoTable = 0;  // table ids start at 1
+  EcdsaEngine() = default;
+
+  void open() {
+    std::lock_guard<std::mutex> g(mu_);
+    if (ctx_) return;
+    const char* e = std::getenv("CBFT_DEVICE");
+    const int rc = cbft_open(&ctx_, e ? std::atoi(e) : 0, 0);
+    if (rc != CBFT_OK) {
+      ctx_ = nullptr;
+      fail("cbft_open", rc);
+    }
+  }
+
+  void verify(const std::vector<uint32_t>& kidx, const std::vector<uint8_t>& sig, const std::vector<uint8_t>& msg,
+              const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, std::vector<uint8_t>& bitmap) {
+    open();
+    std::shared_lock<std::shared_mutex> rd(tbl_mu_);
+    while (true) {
+      {
+        std::lock_guard<std::mutex> g(mu_);
+        if (loaded_ == pubs_.size() / 64 && table_ != kNoTable) break;
+      }
+      rd.unlock();
+      refreshTable();  // builds beside the old table; verifies keep using it meanwhile
+      rd.lock();
+    }
+    const int rc = cbft_ecdsa_verify_batch(ctx_, table_, kidx.data(), sig.data(), msg.data(), off.data(), len.data(),
+                                           kidx.size(), bitmap.data());
+    if (rc != CBFT_OK) fail("cbft_ecdsa_verify_batch", rc);
+  }
+
+  // Rebuild the device key table for the keys registered so far without blocking verifies (as
+  // RsaEngine::refreshTable): records are 1 KB each and built by one kernel launch.
+  void refreshTable() {
+    std::lock_guard<std::mutex> b(build_mu_);
+    std::vector<uint8_t> pubs;
+    {
+      std::lock_guard<std::mutex> g(mu_);
+      if (loaded_ == pubs_.size() / 64 && table_ != kNoTable) return;
+      pubs = pubs_;
+    }
+    uint32_t id;
+    const int rc = cbft_ecdsa_load_keys(ctx_, pubs.data(), (uint32_t)(pubs.size() / 64), &id);
+    if (rc != CBFT_OK) fail("cbft_ecdsa_load_keys", rc);
+    uint32_t old;
+    {
+      std::unique_lock<std::shared_mutex> wr(tbl_mu_);
+      std::lock_guard<std::mutex> g(mu_);
+      old = table_;
+      table_ = id;
+      loaded_ = (uint32_t)(pubs.size() / 64);
+    }
+    if (old != kNoTable) cbft_ecdsa_unload_keys(ctx_, old);  // readers now see table_ = id
+  }
+
+  cbft_ctx* ctx_ = nullptr;
+  std::mutex mu_;             // guards ctx_ (opening), pubs_, index_, table_, loaded_
+  std::shared_mutex tbl_mu_;  // device table lifetime vs in-flight verifies
+  std::mutex build_mu_;       // one table rebuild at a time
+  std::vector<uint8_t> pubs_;
+  std::map<std::string, uint32_t> index_;
+  uint32_t table_ = kNoTable;
+  uint32_t loaded_ = 0;
+  std::atomic<uint64_t> gpu_errors_{0};
+};
+
+HipECDSAVerifier::HipECDSAVerifier(const std::string& str_pub_key, KeyFormat fmt) : key_str_(str_pub_key) {
+  EVP_PKEY* k = parseEcPublicKey(str_pub_key, fmt);
+  char group[80] = {0};
+  size_t glen = 0;
+  BIGNUM *order = nullptr, *x = nullptr, *y = nullptr;
+  bool ok = k && EVP_PKEY_get_base_id(k) == EVP_PKEY_EC &&
+            EVP_PKEY_get_utf8_string_param(k, OSSL_PKEY_PARAM_GROUP_NAME, group, sizeof group, &glen) == 1 &&
+            EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_EC_ORDER, &order) == 1;
+  if (ok) sig_len_ = 2u * (uint32_t)BN_num_bytes(order);
+  BN_free(order);
+  if (ok && std::strcmp(group, "secp256k1") == 0) {
+    uint8_t pub[64];
+    ok = EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_EC_PUB_X, &x) == 1 &&
+         EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_EC_PUB_Y, &y) == 1 && BN_bn2binpad(x, pub, 32) == 32 &&
+         BN_bn2binpad(y, pub + 32, 32) == 32;
+    BN_free(x);
+    BN_free(y);
+    if (ok) {
+      engine_ = EcdsaEngine::get();
+      key_index_ = engine_->registerKey(pub);
+      gpu_capable_ = true;
+    }
+  }
+  if (ok) {
+    pkey_ = k;  // the host path: other curves, and secp256k1 below gpuMinBatch()
+  } else {
+    EVP_PKEY_free(k);
+  }
+  if (!ok) throw std::invalid_argument("HipECDSAVerifier: not an EC public key on a named curve");
+}
+
+HipECDSAVerifier::~HipECDSAVerifier() { EVP_PKEY_free(static_cast<EVP_PKEY*>(pkey_)); }
+
+size_t HipECDSAVerifier::gpuMinBatch() {
+  static const size_t v = [] {
+    const char* e = std::getenv("CBFT_ECDSA_GPU_MIN");
+    const long long x = e ? std::atoll(e) : 0;
+    return x > 0 ? (size_t)x : (size_t)CBFT_ECDSA_GPU_MIN_DEFAULT;
+  }();
+  return v;
+}
+
+// r || s -> DER, then EVP_DigestVerify (SHA-256) on the host
+bool HipECDSAVerifier::verifyHost(const char* data, size_t len, const char* sig, size_t sig_len) const {
+  if (!pkey_ || sig_len != sig_len_) return false;
+  const size_t half = sig_len_ / 2;
+  const unsigned char* sb = reinterpret_cast<const unsigned char*>(sig);
+  BIGNUM* r = BN_bin2bn(sb, (int)half, nullptr);
+  BIGNUM* s = BN_bin2bn(sb + half, (int)half, nullptr);
+  ECDSA_SIG* es = ECDSA_SIG_new();
+  bool ok = false;
+  if (r && s && es && ECDSA_SIG_set0(es, r, s) == 1) {
+    r = s = nullptr;  // owned by es
+    unsigned char* der = nullptr;
+    const int dl = i2d_ECDSA_SIG(es, &der);
+    if (dl > 0) {
+      EVP_MD_CTX* md = EVP_MD_CTX_new();
+      ok = md && EVP_DigestVerifyInit(md, nullptr, EVP_sha256(), nullptr, static_cast<EVP_PKEY*>(pkey_)) == 1 &&
+           EVP_DigestVerify(md, der, (size_t)dl, reinterpret_cast<const unsigned char*>(data), len) == 1;
+      EVP_MD_CTX_free(md);
+    }
+    OPENSSL_free(der);
+  }
+  BN_free(r);
+  BN_free(s);
+  ECDSA_SIG_free(es);
+  return ok;
+}
+
+bool HipECDSAVerifier::verify(const std::string& data, const std::string& sig) const {
+  std::vector<VerifyRequest> r{{this, data.data(), data.size(), sig.data(), sig.size()}};
+  std::vector<bool> out;
+  verifyBatch(r, out);
+  return out[0];
+}
+
+void HipECDSAVerifier::verifyBatch(const std::vector<VerifyRequest>& reqs, std::vector<bool>& out) {
+  out.assign(reqs.size(), false);
+  std::vector<size_t> pos;
+  std::shared_ptr<EcdsaEngine> engine;
+  size_t blob = 0;
+  for (size_t i = 0; i < reqs.size(); i++) {
+    auto v = dynamic_cast<const HipECDSAVerifier*>(reqs[i].verifier);
+    if (!v) continue;
+    if (!v->gpu_capable_) {
+      out[i] = v->verifyHost(reqs[i].data, reqs[i].dataLength, reqs[i].sig, reqs[i].sigLength);
+      continue;
+    }
+    if (reqs[i].sigLength != CBFT_ECDSA_SIGNATURE_BYTES || reqs[i].dataLength > 0xFFFFFF00u) continue;
+    engine = v->engine_;
+    pos.push_back(i);
+    blob += reqs[i].dataLength;
+  }
+  if (pos.empty()) return;
+  const size_t n = pos.size();
+  if (n < gpuMinBatch()) {  // a host loop is faster than one GPU call
+    for (size_t i : pos)
+      out[i] = static_cast<const HipECDSAVerifier*>(reqs[i].verifier)
+                   ->verifyHost(reqs[i].data, reqs[i].dataLength, reqs[i].sig, reqs[i].sigLength);
+    return;
+  }
+  std::vector<uint32_t> kidx(n), len(n);
+  std::vector<uint64_t> off(n);
+  std::vector<uint8_t> sig(n * CBFT_ECDSA_SIGNATURE_BYTES), msg(blob ? blob : 1), bitmap((n + 7) / 8);
+  size_t o = 0;
+  for (size_t j = 0; j < n; j++) {
+    const VerifyRequest& r = reqs[pos[j]];
+    kidx[j] = static_cast<const HipECDSAVerifier*>(r.verifier)->key_index_;
+    std::memcpy(&sig[CBFT_ECDSA_SIGNATURE_BYTES * j], r.sig, CBFT_ECDSA_SIGNATURE_BYTES);
+    off[j] = o;
+    len[j] = (uint32_t)r.dataLength;
+    if (r.dataLength) std::memcpy(&msg[o], r.data, r.dataLength);
+    o += r.dataLength;
+  }
+  engine->verifyNoThrow(kidx, sig, msg, off, len, bitmap);
+  for (size_t j = 0; j < n; j++) out[pos[j]] = (bitmap[j >> 3] >> (j & 7)) & 1;
+}
+
+}  // namespace concord::hip

@@ -428,7 +428,7 @@ std::unique_ptr<ISigner> makeSigner(const std::string& str_priv_key, KeyFormat f
 void verifyBatch(const std::vector<VerifyRequest>& reqs, std::vector<bool>& out) {
   LatencyHistogram::Scope timer(recorders().verify_batch);
   out.assign(reqs.size(), false);
-  bool any_ed = false, any_rsa = false;
+  bool any_ed = false, any_rsa = false, any_ecdsa = false;
   for (size_t i = 0; i < reqs.size(); i++) {
     const IVerifier* v = reqs[i].verifier;
     if (!v) continue;
@@ -436,6 +436,8 @@ void verifyBatch(const std::vector<VerifyRequest>& reqs, std::vector<bool>& out)
       any_ed = true;
     } else if (dynamic_cast<const HipRSAVerifier*>(v)) {
       any_rsa = true;
+    } else if (dynamic_cast<const HipECDSAVerifier*>(v)) {
+      any_ecdsa = true;
     } else {
       out[i] = v->verify(std::string(reqs[i].data, reqs[i].dataLength), std::string(reqs[i].sig, reqs[i].sigLength));
     }
@@ -450,6 +452,11 @@ void verifyBatch(const std::vector<VerifyRequest>& reqs, std::vector<bool>& out)
     HipRSAVerifier::verifyBatch(reqs, part);
     for (size_t i = 0; i < reqs.size(); i++)
       if (dynamic_cast<const HipRSAVerifier*>(reqs[i].verifier)) out[i] = part[i];
+  }
+  if (any_ecdsa) {
+    HipECDSAVerifier::verifyBatch(reqs, part);
+    for (size_t i = 0; i < reqs.size(); i++)
+      if (dynamic_cast<const HipECDSAVerifier*>(reqs[i].verifier)) out[i] = part[i];
   }
 }
 

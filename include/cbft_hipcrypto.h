@@ -485,6 +485,47 @@ int cbft_bls_verify_fixed_device(cbft_ctx* ctx, uint32_t keyset, const uint32_t*
                                  const uint8_t* d_msg, uint32_t msg_len, size_t m, const uint32_t* d_msg_of, size_t n,
                                  uint8_t* d_valid, void* stream);
 
+/* ------------------------------------------------------- ECDSA secp256k1 / SHA-256 ------------
+ * Replaces concord::util::crypto::ECDSAVerifier (util/src/crypto_utils.cpp:34-64,231-236), i.e.
+ * Crypto++ ECDSA<ECP, SHA256> on its default curve secp256k1.  Verdicts are those of OpenSSL 3.0.2
+ * ECDSA_do_verify (tests/golden/ecdsa_vectors.json, restated in tests/ecdsa_ref.py):
+ *   the key is on the curve with X, Y < p;  1 <= r < n and 1 <= s < n;  with e = SHA-256(m) as an
+ *   integer, w = s^-1, u1 = e w, u2 = r w (mod n):  R = u1 G + u2 Q is not infinity and
+ *   x(R) mod n == r.
+ * There is no low-s rule (s and n - s both verify).  A public key is 64 bytes, X || Y big-endian; a
+ * signature is 64 bytes, r || s big-endian (IEEE P1363; IVerifier::signatureLength() == 64).  A
+ * verdict never depends on the other items of its batch. */
+#define CBFT_ECDSA_PUBLIC_KEY_BYTES 64
+#define CBFT_ECDSA_SIGNATURE_BYTES 64
+#define CBFT_ECDSA_MAX_KEYS (1u << 20)            /* keys per table (CBFT_E2BIG) */
+#define CBFT_ECDSA_MAX_BATCH ((size_t)1 << 26)    /* signatures per call (CBFT_E2BIG) */
+
+/* Load nkeys public keys (pub = nkeys x 64 bytes).  Each key is validated and its window table
+ * (the affine multiples 1..15 of Q, 1 KB) is built on the GPU here, once.  A key with a coordinate
+ * >= p or off the curve ((0, 0) included) is accepted into the table and every signature under it
+ * verifies false (cbft_ecdsa_key_status). */
+int cbft_ecdsa_load_keys(cbft_ctx* ctx, const uint8_t* pub, uint32_t nkeys, uint32_t* out_key_table_id);
+/* out_ok: nkeys bytes, 1 = the key is usable */
+int cbft_ecdsa_key_status(cbft_ctx* ctx, uint32_t key_table_id, uint8_t* out_ok);
+int cbft_ecdsa_unload_keys(cbft_ctx* ctx, uint32_t key_table_id);
+
+/* Verify n signatures (sig = n x 64 bytes) against keys of a loaded table; message i =
+ * msg_blob[msg_off[i] .. + msg_len[i]); verdict_bitmap as for Ed25519.  key_idx[i] >= nkeys is
+ * CBFT_EINVAL; n = 0 is CBFT_OK; n > CBFT_ECDSA_MAX_BATCH is CBFT_E2BIG.  Multi-GPU contexts shard
+ * the batch statically, like the RSA and Ed25519 batch verifies. */
+int cbft_ecdsa_verify_batch(cbft_ctx* ctx, uint32_t key_table_id, const uint32_t* key_idx, const uint8_t* sig,
+                            const uint8_t* msg_blob, const uint64_t* msg_off, const uint32_t* msg_len, size_t n,
+                            uint8_t* verdict_bitmap);
+/* Device-resident variant (asynchronous on `stream`, nullptr = the context's own; ceil(n/64)
+ * verdict words); an out-of-range key index verifies false.  Calls on different streams share the
+ * digest scratch and are ordered by the library.  Single-GPU contexts only (CBFT_EINVAL). */
+int cbft_ecdsa_verify_batch_device(cbft_ctx* ctx, uint32_t key_table_id, const uint32_t* d_key_idx,
+                                   const uint8_t* d_sig, const uint8_t* d_msg_blob, const uint64_t* d_msg_off,
+                                   const uint32_t* d_msg_len, size_t n, uint64_t* d_verdict_words, void* stream);
+/* With profiling enabled (cbft_set_profiling): the duration in ms of the last ECDSA batch's kernels
+ * (hash + verify). */
+int cbft_ecdsa_kernel_ms(cbft_ctx* ctx, float* out_ms);
+
 #ifdef __cplusplus
 }
 #endif
