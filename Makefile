@@ -210,7 +210,12 @@ SIGN_SELFTEST := tests/hip/libsign_selftest.so
 RSA_SIGN_SELFTEST := tests/hip/librsa_sign_selftest.so
 BLS_SIGN_SELFTEST := tests/hip/libbls_sign_selftest.so
 BLS_VERIFY_SELFTEST := tests/hip/libbls_verify_selftest.so
-selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST)
+FE25519_SELFTEST := tests/hip/libfe25519_selftest.so
+selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST) $(FE25519_SELFTEST)
+# test-only device harness of the Ed25519 field, scalar and point lane code, one function per launch
+# (tests/test_fe25519_lane_gpu.py); ed25519_verify.o's flags, so ge_frombytes_row is compiled as in the product
+$(FE25519_SELFTEST): tests/hip/fe25519_selftest.hip $(CSRC)/fe25519*.h $(CSRC)/ge25519.h $(CSRC)/sc25519.h $(CSRC)/safegcd30.h $(CSRC)/fe25519_row.h $(CSRC)/row_lanes.h
+	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -shared -o $@ $<
 $(SELFTEST): tests/hip/inv_selftest.hip $(CSRC)/safegcd30.h
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 # test-only device harness of the signing comb and sc_muladd (tests/test_ed25519_sign_gpu.py)
