@@ -12,15 +12,17 @@ ORACLE_LIB := oracle/libcbft_oracle.so
 # host SIMD emulation of the same source is exact).  Costs one v_mov_dpp per move.
 ROWFLAGS := -mllvm -amdgpu-dpp-combine=false
 
-.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim sanitize selftest
-all: lib oracle cpu host shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim selftest
+.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim host_util_test sanitize selftest
+all: lib oracle cpu host shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim host_util_test selftest
 
 lib: $(LIB)
 
 $(CSRC)/ed25519_verify.o: $(CSRC)/ed25519_verify.hip $(CSRC)/*.h
 	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_hipcrypto.o: $(CSRC)/cbft_hipcrypto.cpp include/cbft_hipcrypto.h $(CSRC)/ed25519_verify.h $(CSRC)/cbft_internal.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
+# what every front end (cbft_*.cpp) compiles in through cbft_internal.h
+INTERNAL_DEPS := $(CSRC)/cbft_internal.h $(CSRC)/cbft_host_util.h include/cbft_hipcrypto.h $(CSRC)/ed25519_sign.h $(CSRC)/ed25519_verify.h $(CSRC)/rsa_sign.h $(CSRC)/rsa_verify.h
+$(CSRC)/cbft_hipcrypto.o: $(CSRC)/cbft_hipcrypto.cpp $(INTERNAL_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 BLS_DEPS := $(CSRC)/bls_kernels.h $(CSRC)/bls_common.h $(CSRC)/bn254_*.h $(CSRC)/row_lanes.h $(CSRC)/bls_ops.h $(CSRC)/sha256.h $(CSRC)/bls_glv.h
@@ -43,31 +45,31 @@ $(CSRC)/rsa_verify.o: $(CSRC)/rsa_verify.hip $(CSRC)/rsa_verify.h $(CSRC)/sha256
 $(CSRC)/ed25519_sign.o: $(CSRC)/ed25519_sign.hip $(CSRC)/ed25519_sign.h $(CSRC)/ge25519.h $(CSRC)/fe25519*.h $(CSRC)/sc25519.h $(CSRC)/sha512.h $(CSRC)/safegcd30.h $(CSRC)/row_lanes.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_ed25519_sign.o: $(CSRC)/cbft_ed25519_sign.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
+$(CSRC)/cbft_ed25519_sign.o: $(CSRC)/cbft_ed25519_sign.cpp $(INTERNAL_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # RSA signing: its own object (constant-time CRT kernels; rsa_verify.hip is not touched)
 $(CSRC)/rsa_sign.o: $(CSRC)/rsa_sign.hip $(CSRC)/rsa_sign.h $(CSRC)/sha256.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_rsa_sign.o: $(CSRC)/cbft_rsa_sign.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/rsa_sign.h $(CSRC)/rsa_verify.h
+$(CSRC)/cbft_rsa_sign.o: $(CSRC)/cbft_rsa_sign.cpp $(INTERNAL_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_rsa.o: $(CSRC)/cbft_rsa.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
+$(CSRC)/cbft_rsa.o: $(CSRC)/cbft_rsa.cpp $(INTERNAL_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # BLS share signing in batches: its own object (constant-time lane code; the other BLS kernels are not touched)
 $(CSRC)/bls_sign_batch.o: $(CSRC)/bls_sign_batch.hip $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_bls_sign.o: $(CSRC)/cbft_bls_sign.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/bls_sign_batch.h $(CSRC)/bls_kernels.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
+$(CSRC)/cbft_bls_sign.o: $(CSRC)/cbft_bls_sign.cpp $(INTERNAL_DEPS) $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # BLS verification in batches over many messages: its own objects (the other BLS kernels are not touched)
 $(CSRC)/bls_verify_batch.o: $(CSRC)/bls_verify_batch.hip $(CSRC)/bls_verify_batch.h $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_bls_verify_batch.o: $(CSRC)/cbft_bls_verify_batch.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(CSRC)/bls_verify_batch.h $(CSRC)/bls_kernels.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
+$(CSRC)/cbft_bls_verify_batch.o: $(CSRC)/cbft_bls_verify_batch.cpp $(INTERNAL_DEPS) $(CSRC)/bls_verify_batch.h $(CSRC)/bls_kernels.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # ECDSA secp256k1 verification: its own objects (no other kernel is touched)
@@ -75,10 +77,10 @@ ECDSA_DEPS := $(CSRC)/ecdsa_verify.h $(CSRC)/fe_secp256k1.h $(CSRC)/sc_secp256k1
 $(CSRC)/ecdsa_verify.o: $(CSRC)/ecdsa_verify.hip $(ECDSA_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_ecdsa.o: $(CSRC)/cbft_ecdsa.cpp $(CSRC)/cbft_internal.h include/cbft_hipcrypto.h $(ECDSA_DEPS) $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h $(CSRC)/rsa_sign.h
+$(CSRC)/cbft_ecdsa.o: $(CSRC)/cbft_ecdsa.cpp $(INTERNAL_DEPS) $(ECDSA_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(CSRC)/cbft_internal.h $(CSRC)/rsa_verify.h $(CSRC)/ed25519_sign.h include/cbft_hipcrypto.h $(CSRC)/bls_kernels.h $(CSRC)/rsa_sign.h
+$(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(INTERNAL_DEPS) $(CSRC)/bls_kernels.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o
@@ -177,6 +179,13 @@ $(ECDSA_SHIM): tests/cpp/ecdsa_shim.cpp $(ECDSA_DEPS)
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $<
 $(ECDSA_SHIM_SAN): tests/cpp/ecdsa_shim.cpp $(ECDSA_DEPS)
 	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DECDSA_SHIM_MAIN -I$(CSRC) -o $@ $<
+
+# the front ends' HIP-free helpers (cbft_host_util.h) as a stand-alone program under ASan + UBSan
+# (run by tests/test_host_util_cpu.py, never loaded into python)
+HOST_UTIL_TEST := tests/cpp/host_util_test
+host_util_test: $(HOST_UTIL_TEST)
+$(HOST_UTIL_TEST): tests/cpp/host_util_test.cpp $(CSRC)/cbft_host_util.h
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -I$(CSRC) -o $@ $<
 
 # Host-layer sanitizer builds (host code only: the HIP library itself is not instrumented).
 # ASan+UBSan and TSan variants of the C++ host library and its tests; run on a GPU box with

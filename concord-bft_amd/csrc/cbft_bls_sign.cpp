@@ -15,7 +15,6 @@
 // hash points; their odd multiples live in LDS); it is cleared with the records all the same.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -25,49 +24,29 @@
 
 static_assert(CBFT_BLS_SHARE_BYTES == 37 && CBFT_BLS_G2_BYTES == 65, "sizes");
 
-// memset the optimiser may not drop
-static void wipe(void* p, size_t n) {
-  volatile uint8_t* v = static_cast<volatile uint8_t*>(p);
-  for (size_t i = 0; i < n; i++) v[i] = 0;
-}
-
 static int bls_sign_launch_locked(cbft_ctx* c, BlsSignerTable& st, const uint32_t* d_idx, const uint8_t* d_msg,
                                   const uint64_t* d_off, const uint32_t* d_len, uint32_t fixed_len, size_t n,
                                   uint8_t* d_out, hipStream_t s) {
-  CBFT_HIP(c->blss_scratch.reserve(cbft_bls_sign_scratch_words(n) * sizeof(uint32_t)));
-  if (!c->blss_done) CBFT_HIP(hipEventCreateWithFlags(&c->blss_done, hipEventDisableTiming));
-  if (c->blss_used) CBFT_HIP(hipStreamWaitEvent(s, c->blss_done, 0));  // scratch reuse across streams
+  CBFT_HIP(c->blss.scratch.acquire(cbft_bls_sign_scratch_words(n) * sizeof(uint32_t), s));
   BlsSignBatch b{n, st.rec.as<uint32_t>(), st.nkeys, d_idx, d_msg, d_off, d_len, fixed_len};
-  CBFT_HIP(cbft_bls_sign_launch(b, c->blss_scratch.as<uint32_t>(), d_out, nullptr, s));
-  CBFT_HIP(hipEventRecord(c->blss_done, s));
-  c->blss_used = true;
+  CBFT_HIP(cbft_bls_sign_launch(b, c->blss.scratch.buf.as<uint32_t>(), d_out, nullptr, s));
+  CBFT_HIP(c->blss.scratch.commit(s));
   return CBFT_OK;
 }
 
-// every stream that may still touch the signing state has drained (device-path batches run on
-// caller streams), then the scratch is overwritten
-static void bls_sign_clear_scratch(cbft_ctx* c) {
-  (void)hipDeviceSynchronize();
-  if (c->blss_scratch.p) (void)hipMemsetAsync(c->blss_scratch.p, 0, c->blss_scratch.cap, c->stream);
-}
-
 static void bls_sign_drop_table(cbft_ctx* c, BlsSignerTable& st) {
-  if (st.rec.p) (void)hipMemsetAsync(st.rec.p, 0, st.rec.cap, c->stream);
-  (void)hipStreamSynchronize(c->stream);
-  st.rec.release();
+  cbft_clear_release(st.rec, c->stream);
   st.vk65.release();
 }
 
 void cbft_bls_sign_release(cbft_ctx* c) {
   (void)hipSetDevice(c->device);
-  bls_sign_clear_scratch(c);
+  c->blss.scratch.drain_and_zero(c->stream);
   for (auto& kv : c->bls_signer_tables) bls_sign_drop_table(c, kv.second);
   (void)hipStreamSynchronize(c->stream);
   c->bls_signer_tables.clear();
-  for (DevBuf* b : {&c->blss_scratch, &c->blss_in, &c->blss_out}) b->release();
-  if (c->blss_done) (void)hipEventDestroy(c->blss_done);
-  c->blss_done = nullptr;
-  c->blss_used = false;
+  for (DevBuf* b : {&c->blss.in, &c->blss.out}) b->release();
+  c->blss.scratch.release();
 }
 
 extern "C" {
@@ -93,7 +72,7 @@ int cbft_bls_load_signers(cbft_ctx* c, const uint8_t* sk32, const uint32_t* ids,
     std::memcpy(hs.as<uint8_t>(kbytes), ids, (size_t)nkeys * 4);
   }
   if (e != hipSuccess || !valid) {
-    if (hs.p) wipe(hs.p, hs.cap);
+    if (hs.p) cbft_wipe(hs.p, hs.cap);
     hs.release();
     return e != hipSuccess ? cbft_fail(e, "signer staging", __FILE__, __LINE__) : CBFT_EINVAL;
   }
@@ -118,7 +97,7 @@ int cbft_bls_load_signers(cbft_ctx* c, const uint8_t* sk32, const uint32_t* ids,
   }
   const hipError_t e2 = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = e2;
-  wipe(hs.p, hs.cap);  // the scalars are on the device (or the load failed): none stay here
+  cbft_wipe(hs.p, hs.cap);  // the scalars are on the device (or the load failed): none stay here
   hs.release();
   ds.release();
   if (e != hipSuccess) {
@@ -149,7 +128,8 @@ int cbft_bls_unload_signers(cbft_ctx* c, uint32_t id) {
   auto it = c->bls_signer_tables.find(id);
   if (it == c->bls_signer_tables.end()) return CBFT_EINVAL;
   (void)hipSetDevice(c->device);
-  bls_sign_clear_scratch(c);  // synchronises the device first: in-flight device-path batches read the table
+  // synchronises the device first: in-flight device-path batches read the table
+  c->blss.scratch.drain_and_zero(c->stream);
   bls_sign_drop_table(c, it->second);
   c->bls_signer_tables.erase(it);
   return CBFT_OK;
@@ -163,34 +143,23 @@ int cbft_bls_sign_batch(cbft_ctx* c, uint32_t id, const uint32_t* signer_idx, co
   auto it = c->bls_signer_tables.find(id);
   if (it == c->bls_signer_tables.end()) return CBFT_EINVAL;
   if (n == 0) return CBFT_OK;
-  // the batch's messages are the blob range [lo, hi) its offsets span: only that range moves
-  uint64_t lo = UINT64_MAX, hi = 0;
-  for (size_t i = 0; i < n; i++) {
+  for (size_t i = 0; i < n; i++)
     if (signer_idx && signer_idx[i] >= it->second.nkeys) return CBFT_EINVAL;
-    if (msg_len[i] > CBFT_MAX_MSG_LEN) return CBFT_EINVAL;
-    lo = std::min<uint64_t>(lo, msg_off[i]);
-    hi = std::max<uint64_t>(hi, msg_off[i] + msg_len[i]);
-  }
-  if (hi > lo && !msg_blob) return CBFT_EINVAL;
-  const uint64_t blob = hi > lo ? hi - lo : 0;
-  // one packed device image: offsets (rebased) | lengths | signer indices | blob
-  const size_t o_off = 0, o_len = n * 8, o_idx = o_len + n * 4, o_blob = o_idx + n * 4;
-  CBFT_HIP(hipSetDevice(c->device));
-  CBFT_HIP(c->blss_in.reserve(o_blob + blob + 16));
-  CBFT_HIP(c->blss_out.reserve(n * CBFT_BLS_SHARE_BYTES));
   c->host_off.resize(n);
-  for (size_t i = 0; i < n; i++) c->host_off[i] = msg_off[i] - lo;
-  uint8_t* d = c->blss_in.as<uint8_t>();
-  CBFT_HIP(hipMemcpyAsync(d + o_off, c->host_off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
-  CBFT_HIP(hipMemcpyAsync(d + o_len, msg_len, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (signer_idx) CBFT_HIP(hipMemcpyAsync(d + o_idx, signer_idx, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (blob) CBFT_HIP(hipMemcpyAsync(d + o_blob, msg_blob + lo, blob, hipMemcpyHostToDevice, c->stream));
-  const int rc = bls_sign_launch_locked(c, it->second, signer_idx ? reinterpret_cast<const uint32_t*>(d + o_idx) : nullptr,
-                                        d + o_blob, reinterpret_cast<const uint64_t*>(d + o_off),
-                                        reinterpret_cast<const uint32_t*>(d + o_len), 0, n, c->blss_out.as<uint8_t>(),
+  const CbftSpan span = cbft_msg_span(msg_off, msg_len, n, CBFT_MAX_MSG_LEN, msg_blob != nullptr, c->host_off.data());
+  if (span.err) return CBFT_EINVAL;
+  CBFT_HIP(hipSetDevice(c->device));
+  const CbftPackedArray idx{signer_idx, n * 4};
+  CbftPackedLayout L;
+  CBFT_HIP(cbft_upload_packed(c->blss.in, c->stream, c->host_off.data(), msg_len, n, &idx, 1, msg_blob, span, &L));
+  CBFT_HIP(c->blss.out.reserve(n * CBFT_BLS_SHARE_BYTES));
+  const uint8_t* d = c->blss.in.as<uint8_t>();
+  const int rc = bls_sign_launch_locked(c, it->second, signer_idx ? reinterpret_cast<const uint32_t*>(d + L.mid[0]) : nullptr,
+                                        d + L.blob, reinterpret_cast<const uint64_t*>(d + L.off),
+                                        reinterpret_cast<const uint32_t*>(d + L.len), 0, n, c->blss.out.as<uint8_t>(),
                                         c->stream);
   if (rc) return rc;
-  CBFT_HIP(hipMemcpyAsync(out37, c->blss_out.p, n * CBFT_BLS_SHARE_BYTES, hipMemcpyDeviceToHost, c->stream));
+  CBFT_HIP(hipMemcpyAsync(out37, c->blss.out.p, n * CBFT_BLS_SHARE_BYTES, hipMemcpyDeviceToHost, c->stream));
   CBFT_HIP(hipStreamSynchronize(c->stream));
   return CBFT_OK;
 }

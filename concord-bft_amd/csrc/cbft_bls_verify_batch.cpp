@@ -23,10 +23,8 @@
 void cbft_bls_verify_batch_release(cbft_ctx* c) {
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();  // device-path batches run on caller streams
-  for (DevBuf* b : {&c->blsv_scratch, &c->blsv_in, &c->blsv_out}) b->release();
-  if (c->blsv_done) (void)hipEventDestroy(c->blsv_done);
-  c->blsv_done = nullptr;
-  c->blsv_used = false;
+  for (DevBuf* b : {&c->blsv.in, &c->blsv.out}) b->release();
+  c->blsv.scratch.release();
 }
 
 // the argument checks of the host form that need no device: CBFT_EINVAL before anything is launched
@@ -44,16 +42,13 @@ static int blsv_check(uint32_t nkeys, const uint32_t* key_idx, const uint32_t* m
 
 static int blsv_launch_locked(cbft_ctx* c, BlsKeySet& ks, BlsVerifyBatch b, uint8_t* d_valid, hipStream_t s) {
   if (!c->bls_gen_lines.p) return CBFT_EINVAL;  // built by cbft_bls_load_keys: a key set implies them
-  CBFT_HIP(c->blsv_scratch.reserve(cbft_bls_verify_batch_scratch_bytes(b.n, b.m)));
-  if (!c->blsv_done) CBFT_HIP(hipEventCreateWithFlags(&c->blsv_done, hipEventDisableTiming));
-  if (c->blsv_used) CBFT_HIP(hipStreamWaitEvent(s, c->blsv_done, 0));  // scratch reuse across streams
+  CBFT_HIP(c->blsv.scratch.acquire(cbft_bls_verify_batch_scratch_bytes(b.n, b.m), s));
   b.nkeys = ks.n;
   b.lines = ks.lines.as<uint32_t>();
   b.key_ok = ks.ok.as<uint8_t>();
   b.gen_lines = c->bls_gen_lines.as<uint32_t>();
-  CBFT_HIP(cbft_bls_verify_batch_launch(b, c->blsv_scratch.p, d_valid, s));
-  CBFT_HIP(hipEventRecord(c->blsv_done, s));
-  c->blsv_used = true;
+  CBFT_HIP(cbft_bls_verify_batch_launch(b, c->blsv.scratch.buf.p, d_valid, s));
+  CBFT_HIP(c->blsv.scratch.commit(s));
   return CBFT_OK;
 }
 
@@ -67,41 +62,29 @@ static int blsv_host_one(cbft_ctx* c, uint32_t id, const uint32_t* key_idx, cons
   const int rc0 = blsv_check(it->second.n, key_idx, msg_len, m, msg_of, n);
   if (rc0) return rc0;
   if (n == 0) return CBFT_OK;
-  // the batch's messages are the blob range [lo, hi) their offsets span: only that range moves
-  uint64_t lo = UINT64_MAX, hi = 0;
-  for (size_t j = 0; j < m; j++) {
-    lo = std::min<uint64_t>(lo, msg_off[j]);
-    hi = std::max<uint64_t>(hi, msg_off[j] + msg_len[j]);
-  }
-  if (hi > lo && !msg_blob) return CBFT_EINVAL;
-  const uint64_t blob = hi > lo ? hi - lo : 0;
-  // one packed device image: offsets (rebased) | lengths | key slots | message indices | signatures | blob
-  const size_t o_off = 0, o_len = m * 8, o_key = o_len + m * 4, o_mof = o_key + n * 4, o_sig = o_mof + n * 4,
-               o_blob = o_sig + n * 33;
-  CBFT_HIP(hipSetDevice(c->device));
-  CBFT_HIP(c->blsv_in.reserve(o_blob + blob + 16));
-  CBFT_HIP(c->blsv_out.reserve(n));
+  // no length cap here: blsv_check has applied it
   c->host_off.resize(m);
-  for (size_t j = 0; j < m; j++) c->host_off[j] = msg_off[j] - lo;
-  uint8_t* d = c->blsv_in.as<uint8_t>();
-  CBFT_HIP(hipMemcpyAsync(d + o_off, c->host_off.data(), m * 8, hipMemcpyHostToDevice, c->stream));
-  CBFT_HIP(hipMemcpyAsync(d + o_len, msg_len, m * 4, hipMemcpyHostToDevice, c->stream));
-  if (key_idx) CBFT_HIP(hipMemcpyAsync(d + o_key, key_idx, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (msg_of) CBFT_HIP(hipMemcpyAsync(d + o_mof, msg_of, n * 4, hipMemcpyHostToDevice, c->stream));
-  CBFT_HIP(hipMemcpyAsync(d + o_sig, sig33, n * 33, hipMemcpyHostToDevice, c->stream));
-  if (blob) CBFT_HIP(hipMemcpyAsync(d + o_blob, msg_blob + lo, blob, hipMemcpyHostToDevice, c->stream));
+  const CbftSpan span = cbft_msg_span(msg_off, msg_len, m, 0, msg_blob != nullptr, c->host_off.data());
+  if (span.err) return CBFT_EINVAL;
+  CBFT_HIP(hipSetDevice(c->device));
+  // the packed image's middle arrays: key slots | message indices | signatures
+  const CbftPackedArray mid[3] = {{key_idx, n * 4}, {msg_of, n * 4}, {sig33, n * 33}};
+  CbftPackedLayout L;
+  CBFT_HIP(cbft_upload_packed(c->blsv.in, c->stream, c->host_off.data(), msg_len, m, mid, 3, msg_blob, span, &L));
+  CBFT_HIP(c->blsv.out.reserve(n));
+  const uint8_t* d = c->blsv.in.as<uint8_t>();
   BlsVerifyBatch b{};
   b.n = (uint32_t)n;
   b.m = (uint32_t)m;
-  b.key_idx = key_idx ? reinterpret_cast<const uint32_t*>(d + o_key) : nullptr;
-  b.msg_of = msg_of ? reinterpret_cast<const uint32_t*>(d + o_mof) : nullptr;
-  b.sig33 = d + o_sig;
-  b.msg = d + o_blob;
-  b.off = reinterpret_cast<const uint64_t*>(d + o_off);
-  b.len = reinterpret_cast<const uint32_t*>(d + o_len);
-  const int rc = blsv_launch_locked(c, it->second, b, c->blsv_out.as<uint8_t>(), c->stream);
+  b.key_idx = key_idx ? reinterpret_cast<const uint32_t*>(d + L.mid[0]) : nullptr;
+  b.msg_of = msg_of ? reinterpret_cast<const uint32_t*>(d + L.mid[1]) : nullptr;
+  b.sig33 = d + L.mid[2];
+  b.msg = d + L.blob;
+  b.off = reinterpret_cast<const uint64_t*>(d + L.off);
+  b.len = reinterpret_cast<const uint32_t*>(d + L.len);
+  const int rc = blsv_launch_locked(c, it->second, b, c->blsv.out.as<uint8_t>(), c->stream);
   if (rc) return rc;
-  CBFT_HIP(hipMemcpyAsync(out, c->blsv_out.p, n, hipMemcpyDeviceToHost, c->stream));
+  CBFT_HIP(hipMemcpyAsync(out, c->blsv.out.p, n, hipMemcpyDeviceToHost, c->stream));
   CBFT_HIP(hipStreamSynchronize(c->stream));
   return CBFT_OK;
 }

@@ -11,7 +11,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "cbft_internal.h"
@@ -25,17 +24,14 @@ void cbft_ecdsa_release(cbft_ctx* c) {
   (void)hipDeviceSynchronize();  // device-path batches run on caller streams
   for (auto& kv : c->ecdsa_tables) kv.second.rec.release();
   c->ecdsa_tables.clear();
-  for (DevBuf* b : {&c->ecdsa_gtab, &c->ecdsa_scratch, &c->ecdsa_sig, &c->ecdsa_kidx}) b->release();
-  for (hipEvent_t* e : {&c->ecdsa_done, &c->ecdsa_ev[0], &c->ecdsa_ev[1]}) {
-    if (*e) (void)hipEventDestroy(*e);
-    *e = nullptr;
-  }
-  c->ecdsa_used = c->ecdsa_ev_valid = false;
+  for (DevBuf* b : {&c->ecdsa.gtab, &c->ecdsa.sig, &c->ecdsa.kidx}) b->release();
+  c->ecdsa.scratch.release();
+  c->ecdsa.timer.release();
 }
 
 // G's window table: the record of the key Q = G, built once per context by the key-load kernel
 static int ecdsa_gtab_locked(cbft_ctx* c) {
-  if (c->ecdsa_gtab.p) return CBFT_OK;
+  if (c->ecdsa.gtab.p) return CBFT_OK;
   static const uint8_t g[ECDSA_PUB_BYTES] = ECDSA_G_BYTES;
   DevBuf pub, tab;
   hipError_t e = pub.reserve(ECDSA_PUB_BYTES);
@@ -48,27 +44,19 @@ static int ecdsa_gtab_locked(cbft_ctx* c) {
     tab.release();
     return cbft_fail(e, "ecdsa generator table", __FILE__, __LINE__);
   }
-  c->ecdsa_gtab = tab;
+  c->ecdsa.gtab = tab;
   return CBFT_OK;
 }
 
 static int ecdsa_launch_locked(cbft_ctx* c, EcdsaKeyTable& kt, const uint32_t* d_kidx, const uint8_t* d_sig,
                                const uint8_t* d_msg, const uint64_t* d_off, const uint32_t* d_len, size_t n,
                                uint64_t* d_verdicts, hipStream_t s) {
-  CBFT_HIP(c->ecdsa_scratch.reserve(cbft_ecdsa_scratch_words(n) * sizeof(uint32_t)));
-  if (!c->ecdsa_done) CBFT_HIP(hipEventCreateWithFlags(&c->ecdsa_done, hipEventDisableTiming));
-  if (c->ecdsa_used) CBFT_HIP(hipStreamWaitEvent(s, c->ecdsa_done, 0));  // scratch reuse across streams
-  EcdsaBatch b{n, kt.rec.as<uint32_t>(), kt.nkeys, c->ecdsa_gtab.as<uint32_t>(), d_kidx, d_sig, d_msg, d_off, d_len};
-  if (c->profiling) {
-    if (!c->ecdsa_ev[0])
-      for (hipEvent_t& e : c->ecdsa_ev) CBFT_HIP(hipEventCreate(&e));
-    CBFT_HIP(hipEventRecord(c->ecdsa_ev[0], s));
-  }
-  CBFT_HIP(cbft_ecdsa_launch_verify(b, c->ecdsa_scratch.as<uint32_t>(), d_verdicts, s));
-  if (c->profiling) CBFT_HIP(hipEventRecord(c->ecdsa_ev[1], s));
-  CBFT_HIP(hipEventRecord(c->ecdsa_done, s));
-  c->ecdsa_used = true;
-  c->ecdsa_ev_valid = c->profiling;
+  CBFT_HIP(c->ecdsa.scratch.acquire(cbft_ecdsa_scratch_words(n) * sizeof(uint32_t), s));
+  EcdsaBatch b{n, kt.rec.as<uint32_t>(), kt.nkeys, c->ecdsa.gtab.as<uint32_t>(), d_kidx, d_sig, d_msg, d_off, d_len};
+  CBFT_HIP(c->ecdsa.timer.begin(c->profiling, s));
+  CBFT_HIP(cbft_ecdsa_launch_verify(b, c->ecdsa.scratch.buf.as<uint32_t>(), d_verdicts, s));
+  CBFT_HIP(c->ecdsa.timer.end(c->profiling, s));
+  CBFT_HIP(c->ecdsa.scratch.commit(s));
   return CBFT_OK;
 }
 
@@ -191,41 +179,27 @@ int cbft_ecdsa_verify_batch(cbft_ctx* c, uint32_t id, const uint32_t* key_idx, c
   if (it == c->ecdsa_tables.end()) return CBFT_EINVAL;
   for (size_t i = 0; i < n; i++)
     if (key_idx[i] >= it->second.nkeys) return CBFT_EINVAL;
-  // the batch's messages are the blob range [lo, hi) its offsets span: only that range moves
-  // (a shard of a multi-GPU batch carries its own part of the caller's blob), offsets rebased
-  uint64_t lo = UINT64_MAX, hi = 0;
-  for (size_t i = 0; i < n; i++) {
-    lo = std::min<uint64_t>(lo, msg_off[i]);
-    hi = std::max<uint64_t>(hi, msg_off[i] + msg_len[i]);
-  }
-  if (hi > lo && !msg_blob) return CBFT_EINVAL;
-  const uint64_t blob = hi > lo ? hi - lo : 0;
+  // no cap on a message's length: SHA-256 takes any
   c->host_off.resize(n);
-  for (size_t i = 0; i < n; i++) c->host_off[i] = msg_off[i] - lo;
+  const CbftSpan span = cbft_msg_span(msg_off, msg_len, n, 0, msg_blob != nullptr, c->host_off.data());
+  if (span.err) return CBFT_EINVAL;
   CBFT_HIP(hipSetDevice(c->device));
-  CBFT_HIP(c->ecdsa_kidx.reserve(n * 4));
-  CBFT_HIP(c->ecdsa_sig.reserve(n * ECDSA_SIG_BYTES));
-  CBFT_HIP(c->msg.reserve(blob + 16));
+  CBFT_HIP(c->ecdsa.kidx.reserve(n * 4));
+  CBFT_HIP(c->ecdsa.sig.reserve(n * ECDSA_SIG_BYTES));
+  CBFT_HIP(c->msg.reserve(span.blob + 16));
   CBFT_HIP(c->off.reserve(n * 8));
   CBFT_HIP(c->len.reserve(n * 4));
   CBFT_HIP(c->verdicts.reserve(((n + 63) / 64) * 8));
-  CBFT_HIP(hipMemcpyAsync(c->ecdsa_kidx.p, key_idx, n * 4, hipMemcpyHostToDevice, c->stream));
-  CBFT_HIP(hipMemcpyAsync(c->ecdsa_sig.p, sig, n * ECDSA_SIG_BYTES, hipMemcpyHostToDevice, c->stream));
-  if (blob) CBFT_HIP(hipMemcpyAsync(c->msg.p, msg_blob + lo, blob, hipMemcpyHostToDevice, c->stream));
+  CBFT_HIP(hipMemcpyAsync(c->ecdsa.kidx.p, key_idx, n * 4, hipMemcpyHostToDevice, c->stream));
+  CBFT_HIP(hipMemcpyAsync(c->ecdsa.sig.p, sig, n * ECDSA_SIG_BYTES, hipMemcpyHostToDevice, c->stream));
+  if (span.blob) CBFT_HIP(hipMemcpyAsync(c->msg.p, msg_blob + span.lo, span.blob, hipMemcpyHostToDevice, c->stream));
   CBFT_HIP(hipMemcpyAsync(c->off.p, c->host_off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
   CBFT_HIP(hipMemcpyAsync(c->len.p, msg_len, n * 4, hipMemcpyHostToDevice, c->stream));
-  int rc = ecdsa_launch_locked(c, it->second, c->ecdsa_kidx.as<uint32_t>(), c->ecdsa_sig.as<uint8_t>(),
+  int rc = ecdsa_launch_locked(c, it->second, c->ecdsa.kidx.as<uint32_t>(), c->ecdsa.sig.as<uint8_t>(),
                                c->msg.as<uint8_t>(), c->off.as<uint64_t>(), c->len.as<uint32_t>(), n,
                                c->verdicts.as<uint64_t>(), c->stream);
   if (rc) return rc;
-  const size_t nw = (n + 63) / 64;
-  c->host_verdicts.resize(nw);
-  CBFT_HIP(hipMemcpyAsync(c->host_verdicts.data(), c->verdicts.p, nw * 8, hipMemcpyDeviceToHost, c->stream));
-  CBFT_HIP(hipStreamSynchronize(c->stream));
-  const size_t nbytes = (n + 7) / 8;
-  std::memcpy(bitmap, c->host_verdicts.data(), nbytes);  // little-endian host: words == bytes
-  if (n % 8) bitmap[nbytes - 1] &= (uint8_t)((1u << (n % 8)) - 1);
-  return CBFT_OK;
+  return cbft_fetch_bitmap(c, n, bitmap);
 }
 
 int cbft_ecdsa_verify_batch_device(cbft_ctx* c, uint32_t id, const uint32_t* d_key_idx, const uint8_t* d_sig,
@@ -248,10 +222,9 @@ int cbft_ecdsa_kernel_ms(cbft_ctx* c, float* out_ms) {
   c = cbft_dev0(c);
   if (!c || !out_ms) return CBFT_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
-  if (!c->ecdsa_ev_valid) return CBFT_EINVAL;
+  if (!c->ecdsa.timer.valid) return CBFT_EINVAL;
   CBFT_HIP(hipSetDevice(c->device));
-  CBFT_HIP(hipEventSynchronize(c->ecdsa_ev[1]));
-  CBFT_HIP(hipEventElapsedTime(out_ms, c->ecdsa_ev[0], c->ecdsa_ev[1]));
+  CBFT_HIP(c->ecdsa.timer.elapsed(out_ms));
   return CBFT_OK;
 }
 

@@ -13,7 +13,6 @@
 // by the finish kernel per batch and again with the records when a table is unloaded and at close.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -22,44 +21,24 @@
 
 static_assert(CBFT_ED25519_SIGNATURE_BYTES == 64 && CBFT_ED25519_PUBLIC_KEY_BYTES == 32, "sizes");
 
-// memset the optimiser may not drop
-static void wipe(void* p, size_t n) {
-  volatile uint8_t* v = static_cast<volatile uint8_t*>(p);
-  for (size_t i = 0; i < n; i++) v[i] = 0;
-}
-
 static int sign_launch_locked(cbft_ctx* c, SignerTable& st, const uint32_t* d_idx, const uint8_t* d_msg,
                               const uint64_t* d_off, const uint32_t* d_len, uint32_t fixed_len, size_t n,
                               uint8_t* d_sig, hipStream_t s) {
-  CBFT_HIP(c->sign_scratch.reserve(cbft_ed25519_sign_scratch_words(n) * sizeof(uint32_t)));
-  if (!c->sign_done) CBFT_HIP(hipEventCreateWithFlags(&c->sign_done, hipEventDisableTiming));
-  if (c->sign_used) CBFT_HIP(hipStreamWaitEvent(s, c->sign_done, 0));  // scratch reuse across streams
+  CBFT_HIP(c->sign.scratch.acquire(cbft_ed25519_sign_scratch_words(n) * sizeof(uint32_t), s));
   Ed25519SignBatch b{n, st.rec.as<uint32_t>(), st.nkeys, d_idx, d_msg, d_off, d_len, fixed_len};
-  CBFT_HIP(cbft_ed25519_sign_launch(b, c->sign_table.as<uint32_t>(), c->sign_scratch.as<uint32_t>(), d_sig, s));
-  CBFT_HIP(hipEventRecord(c->sign_done, s));
-  c->sign_used = true;
+  CBFT_HIP(cbft_ed25519_sign_launch(b, c->sign.table.as<uint32_t>(), c->sign.scratch.buf.as<uint32_t>(), d_sig, s));
+  CBFT_HIP(c->sign.scratch.commit(s));
   return CBFT_OK;
-}
-
-// every stream that may still touch the signing state has drained (device-path batches run on
-// caller streams), then the secret buffers are overwritten
-static void sign_clear_scratch(cbft_ctx* c) {
-  (void)hipDeviceSynchronize();
-  if (c->sign_scratch.p) (void)hipMemsetAsync(c->sign_scratch.p, 0, c->sign_scratch.cap, c->stream);
 }
 
 void cbft_sign_release(cbft_ctx* c) {
   (void)hipSetDevice(c->device);
-  sign_clear_scratch(c);
-  for (auto& kv : c->signer_tables)
-    if (kv.second.rec.p) (void)hipMemsetAsync(kv.second.rec.p, 0, kv.second.rec.cap, c->stream);
+  c->sign.scratch.drain_and_zero(c->stream);
+  for (auto& kv : c->signer_tables) cbft_clear_release(kv.second.rec, c->stream);
   (void)hipStreamSynchronize(c->stream);
-  for (auto& kv : c->signer_tables) kv.second.rec.release();
   c->signer_tables.clear();
-  for (DevBuf* b : {&c->sign_table, &c->sign_scratch, &c->sign_in, &c->sign_out}) b->release();
-  if (c->sign_done) (void)hipEventDestroy(c->sign_done);
-  c->sign_done = nullptr;
-  c->sign_used = false;
+  for (DevBuf* b : {&c->sign.table, &c->sign.in, &c->sign.out}) b->release();
+  c->sign.scratch.release();
 }
 
 extern "C" {
@@ -70,12 +49,12 @@ int cbft_ed25519_load_signers(cbft_ctx* c, const uint8_t* seed, uint32_t nkeys, 
   if (nkeys > (1u << 20)) return CBFT_E2BIG;
   std::lock_guard<std::mutex> g(c->mu);
   CBFT_HIP(hipSetDevice(c->device));
-  if (!c->sign_table.p) {
-    CBFT_HIP(c->sign_table.reserve((size_t)CBFT_SIGN_TABLE_WORDS * sizeof(uint32_t)));
-    hipError_t e = cbft_ed25519_sign_build_table(c->sign_table.as<uint32_t>(), c->stream);
+  if (!c->sign.table.p) {
+    CBFT_HIP(c->sign.table.reserve((size_t)CBFT_SIGN_TABLE_WORDS * sizeof(uint32_t)));
+    hipError_t e = cbft_ed25519_sign_build_table(c->sign.table.as<uint32_t>(), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-      c->sign_table.release();
+      c->sign.table.release();
       return cbft_fail(e, "sign comb table", __FILE__, __LINE__);
     }
   }
@@ -92,17 +71,16 @@ int cbft_ed25519_load_signers(cbft_ctx* c, const uint8_t* seed, uint32_t nkeys, 
     e = hipMemcpyAsync(ds.p, hs.p, sbytes, hipMemcpyHostToDevice, c->stream);
   }
   if (e == hipSuccess)
-    e = cbft_ed25519_sign_launch_keys(ds.as<uint8_t>(), nkeys, c->sign_table.as<uint32_t>(), st.rec.as<uint32_t>(),
+    e = cbft_ed25519_sign_launch_keys(ds.as<uint8_t>(), nkeys, c->sign.table.as<uint32_t>(), st.rec.as<uint32_t>(),
                                       c->stream);
   if (e == hipSuccess && ds.p) e = hipMemsetAsync(ds.p, 0, ds.cap, c->stream);
   const hipError_t e2 = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = e2;
-  if (hs.p) wipe(hs.p, hs.cap);  // the seeds are on the device (or the load failed): none stay here
+  if (hs.p) cbft_wipe(hs.p, hs.cap);  // the seeds are on the device (or the load failed): none stay here
   hs.release();
   ds.release();
   if (e != hipSuccess) {
-    if (st.rec.p) (void)hipMemset(st.rec.p, 0, st.rec.cap);
-    st.rec.release();
+    cbft_clear_release(st.rec, c->stream);
     return cbft_fail(e, "signer records", __FILE__, __LINE__);
   }
   const uint32_t id = c->next_signer_id++;
@@ -131,10 +109,9 @@ int cbft_ed25519_unload_signers(cbft_ctx* c, uint32_t id) {
   auto it = c->signer_tables.find(id);
   if (it == c->signer_tables.end()) return CBFT_EINVAL;
   (void)hipSetDevice(c->device);
-  sign_clear_scratch(c);  // synchronises the device first: in-flight device-path batches read the table
-  (void)hipMemsetAsync(it->second.rec.p, 0, it->second.rec.cap, c->stream);
-  (void)hipStreamSynchronize(c->stream);
-  it->second.rec.release();
+  // synchronises the device first: in-flight device-path batches read the table
+  c->sign.scratch.drain_and_zero(c->stream);
+  cbft_clear_release(it->second.rec, c->stream);
   c->signer_tables.erase(it);
   return CBFT_OK;
 }
@@ -147,34 +124,23 @@ int cbft_ed25519_sign_batch(cbft_ctx* c, uint32_t id, const uint32_t* signer_idx
   auto it = c->signer_tables.find(id);
   if (it == c->signer_tables.end()) return CBFT_EINVAL;
   if (n == 0) return CBFT_OK;
-  // the batch's messages are the blob range [lo, hi) its offsets span: only that range moves
-  uint64_t lo = UINT64_MAX, hi = 0;
-  for (size_t i = 0; i < n; i++) {
+  for (size_t i = 0; i < n; i++)
     if (signer_idx && signer_idx[i] >= it->second.nkeys) return CBFT_EINVAL;
-    if (msg_len[i] > CBFT_MAX_MSG_LEN) return CBFT_EINVAL;
-    lo = std::min<uint64_t>(lo, msg_off[i]);
-    hi = std::max<uint64_t>(hi, msg_off[i] + msg_len[i]);
-  }
-  if (hi > lo && !msg_blob) return CBFT_EINVAL;
-  const uint64_t blob = hi > lo ? hi - lo : 0;
-  // one packed device image: offsets (rebased) | lengths | signer indices | blob
-  const size_t o_off = 0, o_len = n * 8, o_idx = o_len + n * 4, o_blob = o_idx + n * 4;
-  CBFT_HIP(hipSetDevice(c->device));
-  CBFT_HIP(c->sign_in.reserve(o_blob + blob + 16));
-  CBFT_HIP(c->sign_out.reserve(n * 64));
   c->host_off.resize(n);
-  for (size_t i = 0; i < n; i++) c->host_off[i] = msg_off[i] - lo;
-  uint8_t* d = c->sign_in.as<uint8_t>();
-  CBFT_HIP(hipMemcpyAsync(d + o_off, c->host_off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
-  CBFT_HIP(hipMemcpyAsync(d + o_len, msg_len, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (signer_idx) CBFT_HIP(hipMemcpyAsync(d + o_idx, signer_idx, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (blob) CBFT_HIP(hipMemcpyAsync(d + o_blob, msg_blob + lo, blob, hipMemcpyHostToDevice, c->stream));
-  const int rc = sign_launch_locked(c, it->second, signer_idx ? reinterpret_cast<const uint32_t*>(d + o_idx) : nullptr,
-                                    d + o_blob, reinterpret_cast<const uint64_t*>(d + o_off),
-                                    reinterpret_cast<const uint32_t*>(d + o_len), 0, n, c->sign_out.as<uint8_t>(),
+  const CbftSpan span = cbft_msg_span(msg_off, msg_len, n, CBFT_MAX_MSG_LEN, msg_blob != nullptr, c->host_off.data());
+  if (span.err) return CBFT_EINVAL;
+  CBFT_HIP(hipSetDevice(c->device));
+  const CbftPackedArray idx{signer_idx, n * 4};
+  CbftPackedLayout L;
+  CBFT_HIP(cbft_upload_packed(c->sign.in, c->stream, c->host_off.data(), msg_len, n, &idx, 1, msg_blob, span, &L));
+  CBFT_HIP(c->sign.out.reserve(n * 64));
+  const uint8_t* d = c->sign.in.as<uint8_t>();
+  const int rc = sign_launch_locked(c, it->second, signer_idx ? reinterpret_cast<const uint32_t*>(d + L.mid[0]) : nullptr,
+                                    d + L.blob, reinterpret_cast<const uint64_t*>(d + L.off),
+                                    reinterpret_cast<const uint32_t*>(d + L.len), 0, n, c->sign.out.as<uint8_t>(),
                                     c->stream);
   if (rc) return rc;
-  CBFT_HIP(hipMemcpyAsync(out_sig, c->sign_out.p, n * 64, hipMemcpyDeviceToHost, c->stream));
+  CBFT_HIP(hipMemcpyAsync(out_sig, c->sign.out.p, n * 64, hipMemcpyDeviceToHost, c->stream));
   CBFT_HIP(hipStreamSynchronize(c->stream));
   return CBFT_OK;
 }

@@ -360,9 +360,9 @@ void cbft_close(cbft_ctx* c) {
   cbft_bls_verify_batch_release(c);
   cbft_ecdsa_release(c);
   for (auto& kv : c->rsa_tables) kv.second.rec.release();
-  for (DevBuf* b : {&c->rsa_scratch, &c->rsa_sig, &c->rsa_kidx}) b->release();
-  for (hipEvent_t e : {c->rsa_done, c->rsa_ev[0], c->rsa_ev[1]})
-    if (e) (void)hipEventDestroy(e);
+  for (DevBuf* b : {&c->rsav.sig, &c->rsav.kidx}) b->release();
+  c->rsav.scratch.release();
+  c->rsav.timer.release();
   for (HostSlot& hs : c->hslots) {
     for (DevBuf* b : {&hs.in, &hs.verd}) b->release();
     hs.pack.release();
@@ -931,7 +931,7 @@ static int submit_host(cbft_ctx* c, uint32_t table_id, const uint8_t* pk, const 
   if (fixed) {
     bhi = (uint64_t)fixed_len * n;
   } else if (n) {
-    blo = UINT64_MAX;
+    blo = msg_off[0];
     lmin = UINT32_MAX;
     for (size_t i = 0; i < n; i++) {
       blo = std::min<uint64_t>(blo, msg_off[i]);

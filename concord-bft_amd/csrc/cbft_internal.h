@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "cbft_hipcrypto.h"
+#include "cbft_host_util.h"
 #include "ed25519_sign.h"
 #include "ed25519_verify.h"
 #include "rsa_sign.h"
@@ -80,6 +81,91 @@ struct DevBuf {
     return static_cast<T*>(p);
   }
 };
+
+// A scratch buffer that the batches of one front end share, whatever streams they run on
+// (device-path batches run on caller streams): the next batch's kernels wait for the previous
+// batch's `done` event before they overwrite it.  acquire(), launch on s, commit().  One guard
+// may order further buffers of the same launch sequence (RSA signing's three).
+#define CBFT_LOCAL __attribute__((visibility("hidden")))  // members stay out of the exported symbols
+struct CBFT_LOCAL ScratchGuard {
+  DevBuf buf;
+  hipEvent_t done = nullptr;
+  bool used = false;
+  hipError_t acquire(size_t bytes, hipStream_t s) {
+    hipError_t e = buf.reserve(bytes);
+    if (e == hipSuccess && !done) e = hipEventCreateWithFlags(&done, hipEventDisableTiming);
+    if (e == hipSuccess && used) e = hipStreamWaitEvent(s, done, 0);
+    return e;
+  }
+  hipError_t commit(hipStream_t s) {
+    hipError_t e = hipEventRecord(done, s);
+    if (e == hipSuccess) used = true;
+    return e;
+  }
+  // every stream that may still touch the front end's state has drained, then the buffer is
+  // overwritten on s (unload and close: a secret scratch keeps nothing of a dropped table)
+  void drain_and_zero(hipStream_t s) {
+    (void)hipDeviceSynchronize();
+    if (buf.p) (void)hipMemsetAsync(buf.p, 0, buf.cap, s);
+  }
+  void release() {
+    buf.release();
+    if (done) (void)hipEventDestroy(done);
+    *this = ScratchGuard{};
+  }
+};
+
+// Events around a front end's last batch when the context is profiling (the *_kernel_ms calls);
+// created at the first profiled batch
+struct CBFT_LOCAL KernelTimer {
+  hipEvent_t ev[2] = {nullptr, nullptr};
+  bool valid = false;
+  hipError_t begin(bool profiling, hipStream_t s) {
+    if (!profiling) return hipSuccess;
+    hipError_t rc = hipSuccess;
+    for (hipEvent_t& e : ev)
+      if (!e && (rc = hipEventCreate(&e)) != hipSuccess) return rc;
+    return hipEventRecord(ev[0], s);
+  }
+  hipError_t end(bool profiling, hipStream_t s) {
+    hipError_t e = profiling ? hipEventRecord(ev[1], s) : hipSuccess;
+    if (e == hipSuccess) valid = profiling;
+    return e;
+  }
+  hipError_t elapsed(float* ms) {
+    hipError_t e = hipEventSynchronize(ev[1]);
+    return e == hipSuccess ? hipEventElapsedTime(ms, ev[0], ev[1]) : e;
+  }
+  void release() {
+    for (hipEvent_t e : ev)
+      if (e) (void)hipEventDestroy(e);
+    *this = KernelTimer{};
+  }
+};
+
+// a secret device buffer (a signer record table) is zeroed on s before it is freed
+static inline void cbft_clear_release(DevBuf& b, hipStream_t s) {
+  if (b.p) (void)hipMemsetAsync(b.p, 0, b.cap, s);
+  (void)hipStreamSynchronize(s);
+  b.release();
+}
+
+// The packed image (cbft_host_util.h) of a host-array batch on the device: one reserve and one copy
+// per array, on s.  `rebased` and `span` come from cbft_msg_span; an array the caller did not give
+// is not copied (the kernel gets a null pointer for it).
+static inline hipError_t cbft_upload_packed(DevBuf& in, hipStream_t s, const uint64_t* rebased, const uint32_t* msg_len,
+                                            size_t m, const CbftPackedArray* mid, size_t n_mid, const uint8_t* msg_blob,
+                                            const CbftSpan& span, CbftPackedLayout* L) {
+  *L = cbft_packed_layout(m, mid, n_mid, span.blob);
+  hipError_t e = in.reserve(L->bytes);
+  uint8_t* d = in.as<uint8_t>();
+  if (e == hipSuccess) e = hipMemcpyAsync(d + L->off, rebased, m * 8, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess) e = hipMemcpyAsync(d + L->len, msg_len, m * 4, hipMemcpyHostToDevice, s);
+  for (size_t k = 0; k < n_mid; k++)
+    if (e == hipSuccess && mid[k].host) e = hipMemcpyAsync(d + L->mid[k], mid[k].host, mid[k].bytes, hipMemcpyHostToDevice, s);
+  if (e == hipSuccess && span.blob) e = hipMemcpyAsync(d + L->blob, msg_blob + span.lo, span.blob, hipMemcpyHostToDevice, s);
+  return e;
+}
 
 // An Ed25519 key table: chunks of CBFT_KEY_CHUNK keys (comb tables of -A, raw keys, decode
 // status; ed25519_verify.h KeyChunks).  Keys are appended into the last chunk / new chunks while
@@ -253,48 +339,48 @@ struct cbft_ctx {
   // RSA
   std::unordered_map<uint32_t, RsaKeyTable> rsa_tables;
   uint32_t next_rsa_id = 1;
-  DevBuf rsa_scratch, rsa_sig, rsa_kidx;
-  hipEvent_t rsa_done = nullptr;  // orders reuse of rsa_scratch across streams
-  bool rsa_used = false;
-  hipEvent_t rsa_ev[2] = {nullptr, nullptr};  // around the last RSA kernel when profiling
-  bool rsa_ev_valid = false;
+  struct {
+    ScratchGuard scratch;  // the batch's working integers (public)
+    DevBuf sig, kidx;      // signatures / indices of a host-array batch
+    KernelTimer timer;     // around the last RSA kernel
+  } rsav;
   // Ed25519 signing (cbft_ed25519_sign.cpp)
   std::unordered_map<uint32_t, SignerTable> signer_tables;
   uint32_t next_signer_id = 1;
-  DevBuf sign_table;                 // comb of B (ed25519_sign.h), built at the first load_signers
-  DevBuf sign_scratch;               // the batch's nonces r: secret, cleared on unload and at close
-  DevBuf sign_in, sign_out;          // packed inputs / signatures of a host-array batch
-  hipEvent_t sign_done = nullptr;    // orders reuse of sign_scratch across streams
-  bool sign_used = false;
+  struct {
+    DevBuf table;          // comb of B (ed25519_sign.h), built at the first load_signers
+    ScratchGuard scratch;  // the batch's nonces r: secret, cleared on unload and at close
+    DevBuf in, out;        // packed inputs / signatures of a host-array batch
+  } sign;
   // RSA signing (cbft_rsa_sign.cpp)
   std::unordered_map<uint32_t, RsaSignerTable> rsa_signer_tables;
   uint32_t next_rsa_signer_id = 1;
-  DevBuf rsas_scratch;               // the batch's window tables: secret, zeroed by the kernel, at unload and close
-  DevBuf rsas_aux, rsas_vscratch;    // fault check: idx | off | len | verdict words | count; verify scratch
-  DevBuf rsas_in, rsas_out;          // packed inputs / signatures of a host-array batch
-  hipEvent_t rsas_done = nullptr;    // orders reuse of the scratch across streams
-  bool rsas_used = false;
+  struct {
+    ScratchGuard scratch;  // the batch's window tables: secret, zeroed by the kernel, at unload and close
+    DevBuf aux, vscratch;  // fault check: idx | off | len | verdict words | count; verify scratch (scratch's event)
+    DevBuf in, out;        // packed inputs / signatures of a host-array batch
+  } rsas;
   // BLS share signing in batches (cbft_bls_sign.cpp)
   std::unordered_map<uint32_t, BlsSignerTable> bls_signer_tables;
   uint32_t next_bls_signer_id = 1;
-  DevBuf blss_scratch;               // the batch's hash points (public)
-  DevBuf blss_in, blss_out;          // packed inputs / shares of a host-array batch
-  hipEvent_t blss_done = nullptr;    // orders reuse of the scratch across streams
-  bool blss_used = false;
+  struct {
+    ScratchGuard scratch;  // the batch's hash points (public; cleared with the records all the same)
+    DevBuf in, out;        // packed inputs / shares of a host-array batch
+  } blss;
   // BLS verification in batches (cbft_bls_verify_batch.cpp)
-  DevBuf blsv_scratch;               // hash points, decoded signatures, gate flags
-  DevBuf blsv_in, blsv_out;          // packed inputs / verdict bytes of a host-array batch
-  hipEvent_t blsv_done = nullptr;    // orders reuse of the scratch across streams
-  bool blsv_used = false;
+  struct {
+    ScratchGuard scratch;  // hash points, decoded signatures, gate flags (public)
+    DevBuf in, out;        // packed inputs / verdict bytes of a host-array batch
+  } blsv;
   // ECDSA secp256k1 verification (cbft_ecdsa.cpp)
   std::unordered_map<uint32_t, EcdsaKeyTable> ecdsa_tables;
   uint32_t next_ecdsa_id = 1;
-  DevBuf ecdsa_gtab;                 // G's window table (the record of the key Q = G), built at the first load
-  DevBuf ecdsa_scratch, ecdsa_sig, ecdsa_kidx;  // digests; signatures / indices of a host-array batch
-  hipEvent_t ecdsa_done = nullptr;   // orders reuse of the scratch across streams
-  bool ecdsa_used = false;
-  hipEvent_t ecdsa_ev[2] = {nullptr, nullptr};  // around the last ECDSA batch's kernels when profiling
-  bool ecdsa_ev_valid = false;
+  struct {
+    DevBuf gtab;           // G's window table (the record of the key Q = G), built at the first load
+    ScratchGuard scratch;  // the batch's digests (public)
+    DevBuf sig, kidx;      // signatures / indices of a host-array batch
+    KernelTimer timer;     // around the last ECDSA batch's kernels
+  } ecdsa;
   DevBuf bls_gen_lines, bls_msg, bls_H, bls_shares, bls_valid, bls_sig, bls_ids, bls_use, bls_lambda,
       bls_partial, bls_out, bls_ms_ok, bls_bitmap, bls_inv, bls_first, bls_flag, bls_g2tmp;
   DevBuf bls_aff;      // the last combine's signature as an affine point (BLS_SIG_WORDS)
@@ -319,6 +405,17 @@ bool cbft_bls_scalar_words(uint32_t* w, const uint8_t* sk32);
     hipError_t _e = (expr);                                                     \
     if (_e != hipSuccess) return cbft_fail(_e, #expr, __FILE__, __LINE__);      \
   } while (0)
+
+// The verdict words of the n-signature batch just queued on c->stream (c->verdicts) -> the
+// caller's bitmap; returns once they are there
+static inline int cbft_fetch_bitmap(cbft_ctx* c, size_t n, uint8_t* bitmap) {
+  const size_t nw = (n + 63) / 64;
+  c->host_verdicts.resize(nw);
+  CBFT_HIP(hipMemcpyAsync(c->host_verdicts.data(), c->verdicts.p, nw * 8, hipMemcpyDeviceToHost, c->stream));
+  CBFT_HIP(hipStreamSynchronize(c->stream));
+  cbft_verdicts_to_bitmap(bitmap, c->host_verdicts.data(), n);
+  return CBFT_OK;
+}
 
 // Run f(kid index) for every device of a multi-GPU context, one host thread per device (each
 // device's calls take its own context mutex, so the devices work concurrently); the first

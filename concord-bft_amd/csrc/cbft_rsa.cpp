@@ -13,7 +13,6 @@
 
 #include <algorithm>
 #include <cstdlib>
-#include <cstring>
 #include <vector>
 
 #include "cbft_internal.h"
@@ -23,20 +22,12 @@ static_assert(CBFT_RSA_MODULUS_BYTES == RSA_MOD_BYTES, "modulus size");
 static int rsa_launch_locked(cbft_ctx* c, RsaKeyTable& kt, const uint32_t* d_kidx, const uint8_t* d_sig,
                              const uint8_t* d_msg, const uint64_t* d_off, const uint32_t* d_len, size_t n,
                              uint64_t* d_verdicts, hipStream_t s) {
-  CBFT_HIP(c->rsa_scratch.reserve(cbft_rsa_scratch_words(n) * sizeof(uint32_t)));
-  if (!c->rsa_done) CBFT_HIP(hipEventCreateWithFlags(&c->rsa_done, hipEventDisableTiming));
-  if (c->rsa_used) CBFT_HIP(hipStreamWaitEvent(s, c->rsa_done, 0));  // scratch reuse across streams
+  CBFT_HIP(c->rsav.scratch.acquire(cbft_rsa_scratch_words(n) * sizeof(uint32_t), s));
   RsaBatch b{n, kt.rec.as<uint32_t>(), kt.nkeys, d_kidx, d_sig, d_msg, d_off, d_len};
-  if (c->profiling) {
-    if (!c->rsa_ev[0])
-      for (hipEvent_t& e : c->rsa_ev) CBFT_HIP(hipEventCreate(&e));
-    CBFT_HIP(hipEventRecord(c->rsa_ev[0], s));
-  }
-  CBFT_HIP(cbft_rsa_launch_verify(b, c->rsa_scratch.as<uint32_t>(), d_verdicts, s));
-  if (c->profiling) CBFT_HIP(hipEventRecord(c->rsa_ev[1], s));
-  CBFT_HIP(hipEventRecord(c->rsa_done, s));
-  c->rsa_used = true;
-  c->rsa_ev_valid = c->profiling;
+  CBFT_HIP(c->rsav.timer.begin(c->profiling, s));
+  CBFT_HIP(cbft_rsa_launch_verify(b, c->rsav.scratch.buf.as<uint32_t>(), d_verdicts, s));
+  CBFT_HIP(c->rsav.timer.end(c->profiling, s));
+  CBFT_HIP(c->rsav.scratch.commit(s));
   return CBFT_OK;
 }
 
@@ -157,41 +148,27 @@ int cbft_rsa_verify_batch(cbft_ctx* c, uint32_t id, const uint32_t* key_idx, con
   if (it == c->rsa_tables.end()) return CBFT_EINVAL;
   for (size_t i = 0; i < n; i++)
     if (key_idx[i] >= it->second.nkeys) return CBFT_EINVAL;
-  // the batch's messages are the blob range [lo, hi) its offsets span: only that range moves
-  // (a shard of a multi-GPU batch carries its own part of the caller's blob), offsets rebased
-  uint64_t lo = UINT64_MAX, hi = 0;
-  for (size_t i = 0; i < n; i++) {
-    lo = std::min<uint64_t>(lo, msg_off[i]);
-    hi = std::max<uint64_t>(hi, msg_off[i] + msg_len[i]);
-  }
-  if (hi > lo && !msg_blob) return CBFT_EINVAL;
-  const uint64_t blob = hi > lo ? hi - lo : 0;
+  // no cap on a message's length: SHA-256 takes any
   c->host_off.resize(n);
-  for (size_t i = 0; i < n; i++) c->host_off[i] = msg_off[i] - lo;
+  const CbftSpan span = cbft_msg_span(msg_off, msg_len, n, 0, msg_blob != nullptr, c->host_off.data());
+  if (span.err) return CBFT_EINVAL;
   CBFT_HIP(hipSetDevice(c->device));
-  CBFT_HIP(c->rsa_kidx.reserve(n * 4));
-  CBFT_HIP(c->rsa_sig.reserve(n * RSA_MOD_BYTES));
-  CBFT_HIP(c->msg.reserve(blob + 16));
+  CBFT_HIP(c->rsav.kidx.reserve(n * 4));
+  CBFT_HIP(c->rsav.sig.reserve(n * RSA_MOD_BYTES));
+  CBFT_HIP(c->msg.reserve(span.blob + 16));
   CBFT_HIP(c->off.reserve(n * 8));
   CBFT_HIP(c->len.reserve(n * 4));
   CBFT_HIP(c->verdicts.reserve(((n + 63) / 64) * 8));
-  CBFT_HIP(hipMemcpyAsync(c->rsa_kidx.p, key_idx, n * 4, hipMemcpyHostToDevice, c->stream));
-  CBFT_HIP(hipMemcpyAsync(c->rsa_sig.p, sig, n * RSA_MOD_BYTES, hipMemcpyHostToDevice, c->stream));
-  if (blob) CBFT_HIP(hipMemcpyAsync(c->msg.p, msg_blob + lo, blob, hipMemcpyHostToDevice, c->stream));
+  CBFT_HIP(hipMemcpyAsync(c->rsav.kidx.p, key_idx, n * 4, hipMemcpyHostToDevice, c->stream));
+  CBFT_HIP(hipMemcpyAsync(c->rsav.sig.p, sig, n * RSA_MOD_BYTES, hipMemcpyHostToDevice, c->stream));
+  if (span.blob) CBFT_HIP(hipMemcpyAsync(c->msg.p, msg_blob + span.lo, span.blob, hipMemcpyHostToDevice, c->stream));
   CBFT_HIP(hipMemcpyAsync(c->off.p, c->host_off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
   CBFT_HIP(hipMemcpyAsync(c->len.p, msg_len, n * 4, hipMemcpyHostToDevice, c->stream));
-  int rc = rsa_launch_locked(c, it->second, c->rsa_kidx.as<uint32_t>(), c->rsa_sig.as<uint8_t>(),
+  int rc = rsa_launch_locked(c, it->second, c->rsav.kidx.as<uint32_t>(), c->rsav.sig.as<uint8_t>(),
                              c->msg.as<uint8_t>(), c->off.as<uint64_t>(), c->len.as<uint32_t>(), n,
                              c->verdicts.as<uint64_t>(), c->stream);
   if (rc) return rc;
-  const size_t nw = (n + 63) / 64;
-  c->host_verdicts.resize(nw);
-  CBFT_HIP(hipMemcpyAsync(c->host_verdicts.data(), c->verdicts.p, nw * 8, hipMemcpyDeviceToHost, c->stream));
-  CBFT_HIP(hipStreamSynchronize(c->stream));
-  const size_t nbytes = (n + 7) / 8;
-  std::memcpy(bitmap, c->host_verdicts.data(), nbytes);  // little-endian host: words == bytes
-  if (n % 8) bitmap[nbytes - 1] &= (uint8_t)((1u << (n % 8)) - 1);
-  return CBFT_OK;
+  return cbft_fetch_bitmap(c, n, bitmap);
 }
 
 int cbft_rsa_verify_batch_device(cbft_ctx* c, uint32_t id, const uint32_t* d_key_idx, const uint8_t* d_sig,
@@ -213,10 +190,9 @@ int cbft_rsa_kernel_ms(cbft_ctx* c, float* out_ms) {
   c = cbft_dev0(c);
   if (!c || !out_ms) return CBFT_EINVAL;
   std::lock_guard<std::mutex> g(c->mu);
-  if (!c->rsa_ev_valid) return CBFT_EINVAL;
+  if (!c->rsav.timer.valid) return CBFT_EINVAL;
   CBFT_HIP(hipSetDevice(c->device));
-  CBFT_HIP(hipEventSynchronize(c->rsa_ev[1]));
-  CBFT_HIP(hipEventElapsedTime(out_ms, c->rsa_ev[0], c->rsa_ev[1]));
+  CBFT_HIP(c->rsav.timer.elapsed(out_ms));
   return CBFT_OK;
 }
 

@@ -14,7 +14,6 @@
 // and at close.
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -22,12 +21,6 @@
 #include "cbft_internal.h"
 
 static_assert(CBFT_RSA_PRIVATE_KEY_BYTES == RSAS_PRIV_BYTES && CBFT_RSA_SIGNATURE_BYTES == 256, "sizes");
-
-// memset the optimiser may not drop
-static void wipe(void* p, size_t n) {
-  volatile uint8_t* v = static_cast<volatile uint8_t*>(p);
-  for (size_t i = 0; i < n; i++) v[i] = 0;
-}
 
 static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
@@ -39,12 +32,10 @@ static int rsa_sign_launch_locked(cbft_ctx* c, RsaSignerTable& st, const uint32_
                                   uint32_t** out_failed, hipStream_t s) {
   const size_t o_idx = 0, o_off = align16(n * 4), o_len = o_off + n * 8, o_verd = align16(o_len + n * 4),
                o_fail = o_verd + ((n + 63) / 64) * 8;
-  CBFT_HIP(c->rsas_scratch.reserve(cbft_rsa_sign_scratch_words(n) * sizeof(uint32_t)));
-  CBFT_HIP(c->rsas_aux.reserve(o_fail + 16));
-  CBFT_HIP(c->rsas_vscratch.reserve(cbft_rsa_scratch_words(n) * sizeof(uint32_t)));
-  if (!c->rsas_done) CBFT_HIP(hipEventCreateWithFlags(&c->rsas_done, hipEventDisableTiming));
-  if (c->rsas_used) CBFT_HIP(hipStreamWaitEvent(s, c->rsas_done, 0));  // scratch reuse across streams
-  uint8_t* aux = c->rsas_aux.as<uint8_t>();
+  CBFT_HIP(c->rsas.aux.reserve(o_fail + 16));
+  CBFT_HIP(c->rsas.vscratch.reserve(cbft_rsa_scratch_words(n) * sizeof(uint32_t)));
+  CBFT_HIP(c->rsas.scratch.acquire(cbft_rsa_sign_scratch_words(n) * sizeof(uint32_t), s));  // orders all three
+  uint8_t* aux = c->rsas.aux.as<uint8_t>();
   uint32_t* v_idx = reinterpret_cast<uint32_t*>(aux + o_idx);
   uint64_t* v_off = reinterpret_cast<uint64_t*>(aux + o_off);
   uint32_t* v_len = reinterpret_cast<uint32_t*>(aux + o_len);
@@ -52,42 +43,30 @@ static int rsa_sign_launch_locked(cbft_ctx* c, RsaSignerTable& st, const uint32_
   uint32_t* failed = reinterpret_cast<uint32_t*>(aux + o_fail);
   RsaSignBatch b{n, st.rec.as<uint32_t>(), st.nkeys, d_idx, d_msg, d_off, d_len, fixed_len};
   if (want_failed) CBFT_HIP(hipMemsetAsync(failed, 0, 4, s));
-  CBFT_HIP(cbft_rsa_sign_launch(b, c->rsas_scratch.as<uint32_t>(), d_sig, s));
+  CBFT_HIP(cbft_rsa_sign_launch(b, c->rsas.scratch.buf.as<uint32_t>(), d_sig, s));
   CBFT_HIP(cbft_rsa_sign_launch_prep(b, v_idx, v_off, v_len, s));
   RsaBatch vb{n, st.vrec.as<uint32_t>(), st.nkeys, v_idx, d_sig, d_msg, v_off, v_len};
-  CBFT_HIP(cbft_rsa_launch_verify(vb, c->rsas_vscratch.as<uint32_t>(), verd, s));
+  CBFT_HIP(cbft_rsa_launch_verify(vb, c->rsas.vscratch.as<uint32_t>(), verd, s));
   CBFT_HIP(cbft_rsa_sign_launch_gate(b, verd, use_status, d_sig, want_failed ? failed : nullptr, s));
-  CBFT_HIP(hipEventRecord(c->rsas_done, s));
-  c->rsas_used = true;
+  CBFT_HIP(c->rsas.scratch.commit(s));
   if (out_verdicts) *out_verdicts = verd;
   if (out_failed) *out_failed = failed;
   return CBFT_OK;
 }
 
-// every stream that may still touch the signing state has drained (device-path batches run on
-// caller streams), then the secret buffers are overwritten
-static void rsa_sign_clear_scratch(cbft_ctx* c) {
-  (void)hipDeviceSynchronize();
-  if (c->rsas_scratch.p) (void)hipMemsetAsync(c->rsas_scratch.p, 0, c->rsas_scratch.cap, c->stream);
-}
-
 static void clear_table(cbft_ctx* c, RsaSignerTable& st) {
-  if (st.rec.p) (void)hipMemsetAsync(st.rec.p, 0, st.rec.cap, c->stream);
-  (void)hipStreamSynchronize(c->stream);
-  st.rec.release();
+  cbft_clear_release(st.rec, c->stream);
   st.vrec.release();
 }
 
 void cbft_rsa_sign_release(cbft_ctx* c) {
   (void)hipSetDevice(c->device);
-  rsa_sign_clear_scratch(c);
+  c->rsas.scratch.drain_and_zero(c->stream);
   for (auto& kv : c->rsa_signer_tables) clear_table(c, kv.second);
   (void)hipStreamSynchronize(c->stream);
   c->rsa_signer_tables.clear();
-  for (DevBuf* b : {&c->rsas_scratch, &c->rsas_aux, &c->rsas_vscratch, &c->rsas_in, &c->rsas_out}) b->release();
-  if (c->rsas_done) (void)hipEventDestroy(c->rsas_done);
-  c->rsas_done = nullptr;
-  c->rsas_used = false;
+  for (DevBuf* b : {&c->rsas.aux, &c->rsas.vscratch, &c->rsas.in, &c->rsas.out}) b->release();
+  c->rsas.scratch.release();
 }
 
 extern "C" {
@@ -139,13 +118,11 @@ int cbft_rsa_load_signers(cbft_ctx* c, const uint8_t* priv, const uint32_t* expo
   }
   const hipError_t e2 = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = e2;
-  if (hs.p) wipe(hs.p, hs.cap);  // the keys are on the device (or the load failed): none stay here
+  if (hs.p) cbft_wipe(hs.p, hs.cap);  // the keys are on the device (or the load failed): none stay here
   hs.release();
   for (DevBuf* b : {&dp, &dex, &dmod, &didx, &dmsg, &dsig}) b->release();
   if (e != hipSuccess || rc != CBFT_OK) {
-    if (st.rec.p) (void)hipMemset(st.rec.p, 0, st.rec.cap);
-    st.rec.release();
-    st.vrec.release();
+    clear_table(c, st);
     return rc != CBFT_OK ? rc : cbft_fail(e, "rsa signer records", __FILE__, __LINE__);
   }
   const uint32_t id = c->next_rsa_signer_id++;
@@ -196,7 +173,8 @@ int cbft_rsa_unload_signers(cbft_ctx* c, uint32_t id) {
   auto it = c->rsa_signer_tables.find(id);
   if (it == c->rsa_signer_tables.end()) return CBFT_EINVAL;
   (void)hipSetDevice(c->device);
-  rsa_sign_clear_scratch(c);  // synchronises the device first: in-flight device-path batches read the table
+  // synchronises the device first: in-flight device-path batches read the table
+  c->rsas.scratch.drain_and_zero(c->stream);
   clear_table(c, it->second);
   c->rsa_signer_tables.erase(it);
   return CBFT_OK;
@@ -212,37 +190,26 @@ int cbft_rsa_sign_batch(cbft_ctx* c, uint32_t id, const uint32_t* signer_idx, co
   if (it == c->rsa_signer_tables.end()) return CBFT_EINVAL;
   if (out_failed && n == 0) *out_failed = 0;
   if (n == 0) return CBFT_OK;
-  // the batch's messages are the blob range [lo, hi) its offsets span: only that range moves
-  uint64_t lo = UINT64_MAX, hi = 0;
-  for (size_t i = 0; i < n; i++) {
+  for (size_t i = 0; i < n; i++)
     if (signer_idx && signer_idx[i] >= it->second.nkeys) return CBFT_EINVAL;
-    if (msg_len[i] > CBFT_MAX_MSG_LEN) return CBFT_EINVAL;
-    lo = std::min<uint64_t>(lo, msg_off[i]);
-    hi = std::max<uint64_t>(hi, msg_off[i] + msg_len[i]);
-  }
-  if (hi > lo && !msg_blob) return CBFT_EINVAL;
-  const uint64_t blob = hi > lo ? hi - lo : 0;
-  // one packed device image: offsets (rebased) | lengths | signer indices | blob
-  const size_t o_off = 0, o_len = n * 8, o_idx = o_len + n * 4, o_blob = o_idx + n * 4;
-  CBFT_HIP(hipSetDevice(c->device));
-  CBFT_HIP(c->rsas_in.reserve(o_blob + blob + 16));
-  CBFT_HIP(c->rsas_out.reserve(n * 256));
   c->host_off.resize(n);
-  for (size_t i = 0; i < n; i++) c->host_off[i] = msg_off[i] - lo;
-  uint8_t* d = c->rsas_in.as<uint8_t>();
-  CBFT_HIP(hipMemcpyAsync(d + o_off, c->host_off.data(), n * 8, hipMemcpyHostToDevice, c->stream));
-  CBFT_HIP(hipMemcpyAsync(d + o_len, msg_len, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (signer_idx) CBFT_HIP(hipMemcpyAsync(d + o_idx, signer_idx, n * 4, hipMemcpyHostToDevice, c->stream));
-  if (blob) CBFT_HIP(hipMemcpyAsync(d + o_blob, msg_blob + lo, blob, hipMemcpyHostToDevice, c->stream));
+  const CbftSpan span = cbft_msg_span(msg_off, msg_len, n, CBFT_MAX_MSG_LEN, msg_blob != nullptr, c->host_off.data());
+  if (span.err) return CBFT_EINVAL;
+  CBFT_HIP(hipSetDevice(c->device));
+  const CbftPackedArray idx{signer_idx, n * 4};
+  CbftPackedLayout L;
+  CBFT_HIP(cbft_upload_packed(c->rsas.in, c->stream, c->host_off.data(), msg_len, n, &idx, 1, msg_blob, span, &L));
+  CBFT_HIP(c->rsas.out.reserve(n * 256));
+  const uint8_t* d = c->rsas.in.as<uint8_t>();
   uint32_t* d_failed = nullptr;
   const int rc = rsa_sign_launch_locked(
-      c, it->second, signer_idx ? reinterpret_cast<const uint32_t*>(d + o_idx) : nullptr, d + o_blob,
-      reinterpret_cast<const uint64_t*>(d + o_off), reinterpret_cast<const uint32_t*>(d + o_len), 0, n,
-      c->rsas_out.as<uint8_t>(), 1, true, nullptr, &d_failed, c->stream);
+      c, it->second, signer_idx ? reinterpret_cast<const uint32_t*>(d + L.mid[0]) : nullptr, d + L.blob,
+      reinterpret_cast<const uint64_t*>(d + L.off), reinterpret_cast<const uint32_t*>(d + L.len), 0, n,
+      c->rsas.out.as<uint8_t>(), 1, true, nullptr, &d_failed, c->stream);
   if (rc) return rc;
   uint32_t failed = 0;
   CBFT_HIP(hipMemcpyAsync(&failed, d_failed, 4, hipMemcpyDeviceToHost, c->stream));
-  CBFT_HIP(hipMemcpyAsync(out_sig, c->rsas_out.p, n * 256, hipMemcpyDeviceToHost, c->stream));
+  CBFT_HIP(hipMemcpyAsync(out_sig, c->rsas.out.p, n * 256, hipMemcpyDeviceToHost, c->stream));
   CBFT_HIP(hipStreamSynchronize(c->stream));
   if (out_failed) *out_failed = failed;
   return CBFT_OK;

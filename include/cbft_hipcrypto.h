@@ -36,7 +36,8 @@ extern "C" {
 #endif
 
 #define CBFT_OK 0
-#define CBFT_EINVAL (-22) /* bad argument (null pointer with n > 0, unknown table id, ...) */
+#define CBFT_EINVAL (-22) /* bad argument (null pointer with n > 0, unknown table id, a host-array
+                             message whose end msg_off[i] + msg_len[i] passes 2^64, ...) */
 #define CBFT_ENOMEM (-12) /* device or host allocation failed */
 #define CBFT_ENODEV (-19) /* no such GPU / HIP runtime unavailable */
 #define CBFT_EIO (-5)     /* a HIP launch or copy failed */
