@@ -12,8 +12,8 @@ ORACLE_LIB := oracle/libcbft_oracle.so
 # host SIMD emulation of the same source is exact).  Costs one v_mov_dpp per move.
 ROWFLAGS := -mllvm -amdgpu-dpp-combine=false
 
-.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim host_util_test sanitize selftest
-all: lib oracle cpu host shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim host_util_test selftest
+.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test sanitize selftest
+all: lib oracle cpu host shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test selftest
 
 lib: $(LIB)
 
@@ -80,10 +80,18 @@ $(CSRC)/ecdsa_verify.o: $(CSRC)/ecdsa_verify.hip $(ECDSA_DEPS)
 $(CSRC)/cbft_ecdsa.o: $(CSRC)/cbft_ecdsa.cpp $(INTERNAL_DEPS) $(ECDSA_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# ECDSA secp256k1 signing: its own objects (constant-time lane code; ecdsa_verify.hip is not touched)
+ECDSA_SIGN_DEPS := $(CSRC)/ecdsa_sign.h $(ECDSA_DEPS)
+$(CSRC)/ecdsa_sign.o: $(CSRC)/ecdsa_sign.hip $(ECDSA_SIGN_DEPS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/cbft_ecdsa_sign.o: $(CSRC)/cbft_ecdsa_sign.cpp $(INTERNAL_DEPS) $(ECDSA_SIGN_DEPS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 $(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(INTERNAL_DEPS) $(CSRC)/bls_kernels.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o
+$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o $(CSRC)/ecdsa_sign.o $(CSRC)/cbft_ecdsa_sign.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle: $(ORACLE_LIB)
@@ -104,6 +112,12 @@ cpu: $(CPU_ECDSA_LIB)
 $(CPU_ECDSA_LIB): tools/cpu_baseline/openssl_ecdsa.c
 	gcc -O2 -std=gnu11 -fPIC -shared -Wall -Wno-deprecated-declarations -o $@ $< -lcrypto -lpthread
 
+# the ECDSA secp256k1 signing host baseline of tools/ecdsa_sign_bench.py (threads of ECDSA_do_sign)
+CPU_ECDSA_SIGN_LIB := tools/cpu_baseline/libcbft_cpu_openssl_ecdsa_sign.so
+cpu: $(CPU_ECDSA_SIGN_LIB)
+$(CPU_ECDSA_SIGN_LIB): tools/cpu_baseline/openssl_ecdsa_sign.c
+	gcc -O2 -std=gnu11 -fPIC -shared -Wall -Wno-deprecated-declarations -o $@ $< -lcrypto -lpthread
+
 # C++ plugin layer.  Product sources (concord::hip, BLS::Hip) compile against the reference's own
 # headers in an integration build (tests/test_reference_boundary.py) and here against the
 # restatements in ref_mirror/ (the reference's util / bftengine / threshsign libraries need
@@ -114,9 +128,9 @@ HOST_SRC := $(HOST_DIR)/src/hip_ed25519.cpp $(HOST_DIR)/src/hip_rsa.cpp $(HOST_D
 MIRROR_SRC := $(wildcard $(HOST_DIR)/ref_mirror/src/*.cpp)
 HOST_INC := -Iinclude -I$(HOST_DIR)/include -I$(HOST_DIR)/ref_mirror/include -DCBFT_WITH_CLIENT_KEYS_MAP
 HOST_HDRS := $(wildcard $(HOST_DIR)/include/*.hpp $(HOST_DIR)/include/threshsign/*.hpp $(HOST_DIR)/ref_mirror/include/*.hpp $(HOST_DIR)/ref_mirror/include/threshsign/*.h)
-host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_ecdsa_host tools/host_bench
-$(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB)
-	g++ -O2 -std=c++17 -fPIC -shared -Wall $(HOST_INC) -o $@ $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN'
+host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_ecdsa_host tests/cpp/test_ecdsa_sign_host tools/host_bench
+$(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB) $(ECDSA_SIGN_DEPS)
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN'
 tests/cpp/test_host: tests/cpp/test_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall -DCONCORD_BFT_TESTING $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
@@ -133,6 +147,9 @@ tests/cpp/test_bls_verify_host: tests/cpp/test_bls_verify_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_ecdsa_host: tests/cpp/test_ecdsa_host.cpp $(HOST_LIB)
+	g++ -O2 -std=c++17 -Wall -Wno-deprecated-declarations $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+tests/cpp/test_ecdsa_sign_host: tests/cpp/test_ecdsa_sign_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall -Wno-deprecated-declarations $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_bls_host: tests/cpp/test_bls_host.cpp $(HOST_LIB)
@@ -180,6 +197,16 @@ $(ECDSA_SHIM): tests/cpp/ecdsa_shim.cpp $(ECDSA_DEPS)
 $(ECDSA_SHIM_SAN): tests/cpp/ecdsa_shim.cpp $(ECDSA_DEPS)
 	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DECDSA_SHIM_MAIN -I$(CSRC) -o $@ $<
 
+# host build of the ECDSA secp256k1 signing lane code (ecdsa_sign.h) for tests/test_ecdsa_sign_cpu.py, and
+# the same source as a stand-alone program under ASan + UBSan (run by that test, never loaded into python)
+ECDSA_SIGN_SHIM := tests/cpp/libecdsa_sign_shim.so
+ECDSA_SIGN_SHIM_SAN := tests/cpp/ecdsa_sign_shim_san
+ecdsa_sign_shim: $(ECDSA_SIGN_SHIM) $(ECDSA_SIGN_SHIM_SAN)
+$(ECDSA_SIGN_SHIM): tests/cpp/ecdsa_sign_shim.cpp $(ECDSA_SIGN_DEPS)
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $< -lpthread
+$(ECDSA_SIGN_SHIM_SAN): tests/cpp/ecdsa_sign_shim.cpp $(ECDSA_SIGN_DEPS)
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DECDSA_SIGN_SHIM_MAIN -I$(CSRC) -o $@ $< -lpthread
+
 # the front ends' HIP-free helpers (cbft_host_util.h) as a stand-alone program under ASan + UBSan
 # (run by tests/test_host_util_cpu.py, never loaded into python)
 HOST_UTIL_TEST := tests/cpp/host_util_test
@@ -220,7 +247,11 @@ RSA_SIGN_SELFTEST := tests/hip/librsa_sign_selftest.so
 BLS_SIGN_SELFTEST := tests/hip/libbls_sign_selftest.so
 BLS_VERIFY_SELFTEST := tests/hip/libbls_verify_selftest.so
 FE25519_SELFTEST := tests/hip/libfe25519_selftest.so
-selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST) $(FE25519_SELFTEST)
+ECDSA_SIGN_SELFTEST := tests/hip/libecdsa_sign_selftest.so
+selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST) $(FE25519_SELFTEST) $(ECDSA_SIGN_SELFTEST)
+# test-only device harness of the ECDSA signing lane code, one function per launch (tests/test_ecdsa_sign_gpu.py)
+$(ECDSA_SIGN_SELFTEST): tests/hip/ecdsa_sign_selftest.hip $(CSRC)/ecdsa_sign.hip $(ECDSA_SIGN_DEPS)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 # test-only device harness of the Ed25519 field, scalar and point lane code, one function per launch
 # (tests/test_fe25519_lane_gpu.py); ed25519_verify.o's flags, so ge_frombytes_row is compiled as in the product
 $(FE25519_SELFTEST): tests/hip/fe25519_selftest.hip $(CSRC)/fe25519*.h $(CSRC)/ge25519.h $(CSRC)/sc25519.h $(CSRC)/safegcd30.h $(CSRC)/fe25519_row.h $(CSRC)/row_lanes.h

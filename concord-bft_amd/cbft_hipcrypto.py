@@ -160,6 +160,17 @@ ABI = [
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_ecdsa_kernel_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
+    ("cbft_ecdsa_load_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _u32p]),
+    ("cbft_ecdsa_signer_status", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("cbft_ecdsa_signer_public_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    ("cbft_ecdsa_unload_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
+    ("cbft_ecdsa_sign_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_size_t, ctypes.c_void_p]),
+    ("cbft_ecdsa_sign_fixed_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t,
+      ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_ecdsa_sign_kernel_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
 ]
 
 # cbft_set_option options (include/cbft_hipcrypto.h, "tuning")
@@ -534,6 +545,52 @@ class Context:
     def ecdsa_kernel_ms(self) -> float:
         out = ctypes.c_float()
         _check(self.lib.cbft_ecdsa_kernel_ms(self.handle, ctypes.byref(out)), "cbft_ecdsa_kernel_ms")
+        return out.value
+
+    # ------------------------------------------------------------------ ECDSA secp256k1 signing (RFC 6979)
+    def ecdsa_load_signers(self, privs) -> int:
+        """privs: 32-byte big-endian private keys; returns the signer table id."""
+        k = _as_rows(privs, 32)
+        tid = ctypes.c_uint32()
+        _check(self.lib.cbft_ecdsa_load_signers(self.handle, _ptr(k), k.shape[0], ctypes.byref(tid)),
+               "cbft_ecdsa_load_signers")
+        return tid.value
+
+    def ecdsa_signer_status(self, tid: int, nkeys: int) -> np.ndarray:
+        out = np.zeros(max(1, nkeys), dtype=np.uint8)
+        _check(self.lib.cbft_ecdsa_signer_status(self.handle, tid, _ptr(out)), "cbft_ecdsa_signer_status")
+        return out[:nkeys].astype(bool)
+
+    def ecdsa_signer_public_keys(self, tid: int, nkeys: int) -> np.ndarray:
+        """(nkeys, 64) uint8: X || Y big-endian, zeros for an unusable key."""
+        out = np.zeros((max(1, nkeys), 64), dtype=np.uint8)
+        _check(self.lib.cbft_ecdsa_signer_public_keys(self.handle, tid, _ptr(out)), "cbft_ecdsa_signer_public_keys")
+        return out[:nkeys]
+
+    def ecdsa_unload_signers(self, tid: int):
+        _check(self.lib.cbft_ecdsa_unload_signers(self.handle, tid), "cbft_ecdsa_unload_signers")
+
+    def ecdsa_sign(self, tid: int, msgs: Sequence[bytes], signer_idx=None) -> np.ndarray:
+        """Signatures (n, 64) uint8 (r || s) of msgs under signer_idx[i] (None: all under signer 0)."""
+        n = len(msgs)
+        blob, offs, lens = pack_messages(msgs)
+        idx = None if signer_idx is None else np.ascontiguousarray(np.asarray(signer_idx, dtype=np.uint32))
+        assert idx is None or idx.shape[0] == n
+        out = np.zeros((max(1, n), 64), dtype=np.uint8)
+        _check(self.lib.cbft_ecdsa_sign_batch(self.handle, tid, None if idx is None else _ptr(idx), _ptr(blob),
+                                               _ptr(offs), _ptr(lens), n, _ptr(out)), "cbft_ecdsa_sign_batch")
+        return out[:n]
+
+    def ecdsa_sign_device(self, tid: int, d_signer_idx, d_msg, msg_len: int, n: int, d_sig, stream=0):
+        """Fixed-length messages (message i at d_msg + i * msg_len), asynchronous on `stream`.  Arrays:
+        torch tensors on this context's GPU or raw device addresses (d_signer_idx may be None)."""
+        _check(self.lib.cbft_ecdsa_sign_fixed_device(
+            self.handle, tid, None if d_signer_idx is None else _dev_ptr(d_signer_idx), _dev_ptr(d_msg), msg_len, n,
+            _dev_ptr(d_sig), ctypes.c_void_p(getattr(stream, "cuda_stream", stream))), "cbft_ecdsa_sign_fixed_device")
+
+    def ecdsa_sign_kernel_ms(self) -> float:
+        out = ctypes.c_float()
+        _check(self.lib.cbft_ecdsa_sign_kernel_ms(self.handle, ctypes.byref(out)), "cbft_ecdsa_sign_kernel_ms")
         return out.value
 
     # ------------------------------------------------------------------ RSA-2048 signing (CRT)

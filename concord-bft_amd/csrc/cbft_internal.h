@@ -262,6 +262,13 @@ struct BlsSignerTable {
   DevBuf rec, vk65;
 };
 
+// ECDSA secp256k1 signer table: per-signer records (x, public key Q = x G, validity) built on the
+// GPU at load time (ecdsa_sign.h ECDSAS_WORDS)
+struct EcdsaSignerTable {
+  uint32_t nkeys = 0;
+  DevBuf rec;
+};
+
 struct cbft_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -381,6 +388,15 @@ struct cbft_ctx {
     DevBuf sig, kidx;      // signatures / indices of a host-array batch
     KernelTimer timer;     // around the last ECDSA batch's kernels
   } ecdsa;
+  // ECDSA secp256k1 signing (cbft_ecdsa_sign.cpp)
+  std::unordered_map<uint32_t, EcdsaSignerTable> ecdsa_signer_tables;
+  uint32_t next_ecdsa_signer_id = 1;
+  struct {
+    DevBuf table;       // comb of G (ecdsa_sign.h), built at the first load_signers; public
+    ScratchGuard scratch;  // the batch's nonces k (secret, zeroed by their reader, at unload and close), digests, states
+    DevBuf in, out;     // packed inputs / signatures of a host-array batch
+    KernelTimer timer;  // around the last signing batch's kernel
+  } ecdsas;
   DevBuf bls_gen_lines, bls_msg, bls_H, bls_shares, bls_valid, bls_sig, bls_ids, bls_use, bls_lambda,
       bls_partial, bls_out, bls_ms_ok, bls_bitmap, bls_inv, bls_first, bls_flag, bls_g2tmp;
   DevBuf bls_aff;      // the last combine's signature as an affine point (BLS_SIG_WORDS)
@@ -396,6 +412,7 @@ void cbft_rsa_sign_release(cbft_ctx* c);
 void cbft_bls_sign_release(cbft_ctx* c);
 void cbft_bls_verify_batch_release(cbft_ctx* c);
 void cbft_ecdsa_release(cbft_ctx* c);
+void cbft_ecdsa_sign_release(cbft_ctx* c);
 // 32-byte big-endian BLS scalar -> 8 little-endian words reduced mod r, as cbft_bls_sign takes it;
 // false for 0 (mod r)
 bool cbft_bls_scalar_words(uint32_t* w, const uint8_t* sk32);

@@ -185,6 +185,50 @@ class HipECDSAVerifier : public IVerifier {
   std::shared_ptr<EcdsaEngine> engine_;
 };
 
+// Smallest secp256k1 HipECDSASigner::signBatch that goes to the GPU ($CBFT_ECDSA_SIGN_GPU_MIN
+// overrides): the measured crossover of one cbft_ecdsa_sign_batch call, host arrays in to host
+// arrays out, against a loop of sign() (the lane code built for the host) on one core, rounded up to
+// a power of two: 16 (profiles/ecdsa_sign.json "crossover").
+#define CBFT_ECDSA_SIGN_GPU_MIN_DEFAULT 16
+
+// ECDSA / SHA-256 signing in place of concord::util::crypto::ECDSASigner (Crypto++ ECDSA<ECP,
+// SHA256>::Signer, util/include/crypto_utils.hpp:71-90).  Signatures are r || s, each as long as the
+// group order.  A secp256k1 key signs with RFC 6979 nonces: sign() runs the GPU's
+// lane code built for the host (the same bytes, the same constant-time construction), signBatch()
+// one GPU call from gpuMinBatch() requests up.  A key on any other curve the host OpenSSL knows
+// (KeyExchangeManager generates secp384r1 keys) signs with OpenSSL on the host only.
+class HipECDSASigner : public ISigner {
+ public:
+  // An EC private key, hex DER (PKCS#8 or RFC 5915) or PEM.  Throws std::invalid_argument unless it
+  // parses as an EC private key on a named curve.
+  HipECDSASigner(const std::string& str_priv_key, KeyFormat fmt);
+  ~HipECDSASigner() override;  // wipes the private scalar
+  HipECDSASigner(const HipECDSASigner&) = delete;
+  HipECDSASigner& operator=(const HipECDSASigner&) = delete;
+
+  std::string sign(const std::string& data) override;
+  // reqs[i].outSig = sign(reqs[i].data) for every request.  secp256k1 and gpuMinBatch() requests or
+  // more: one cbft_ecdsa_sign_batch call on the process's ECDSA engine (the key is loaded into it at
+  // the first such batch); below it, on another curve, or when the GPU call fails (counted in
+  // ecdsaSignStats().gpu_errors), the host loop over sign().  Throws only where sign() throws.
+  void signBatch(const std::vector<SignRequest>& reqs);
+  static size_t gpuMinBatch();
+  uint32_t signatureLength() const override { return sig_len_; }
+  std::string getPrivKey() const override { return key_str_; }
+  bool gpuCapable() const { return gpu_capable_; }
+  // the public key as HipECDSAVerifier takes it (X.509 SubjectPublicKeyInfo, hex DER)
+  std::string getPubKeyHex() const;
+
+ private:
+  std::string key_str_;
+  uint32_t sig_len_ = 0;
+  bool gpu_capable_ = false;
+  void* pkey_ = nullptr;  // EVP_PKEY*
+  uint8_t scalar_[32];    // secp256k1: the private scalar, big-endian; wiped by the destructor
+  std::shared_ptr<EcdsaEngine> engine_;  // set once the key is loaded for signBatch
+  uint32_t signer_table_ = 0;
+};
+
 class EdDSASigner : public ISigner {
  public:
   // 32-byte RFC 8032 seed in hex, or a PKCS#8 PEM private key
@@ -283,6 +327,7 @@ struct SignStats {
 };
 SignStats ed25519SignStats();
 SignStats rsaSignStats();  // the same for HipRSASigner::signBatch
+SignStats ecdsaSignStats();  // the same for HipECDSASigner::signBatch
 
 // Selects the GPU the engines open (default 0; $CBFT_DEVICE overrides).  Call before the first
 // verifier is constructed.

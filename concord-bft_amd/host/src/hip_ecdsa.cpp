@@ -1,10 +1,15 @@
-// HipECDSAVerifier over libcbft_hipcrypto (see hip_crypto.hpp).
+// HipECDSAVerifier and HipECDSASigner over libcbft_hipcrypto (see hip_crypto.hpp).
 //
 // Reference: concord::util::crypto::ECDSAVerifier (util/src/crypto_utils.cpp:34-64,231-236):
 // Crypto++ ECDSA<ECP, SHA256>, default curve secp256k1, keyed from hex DER (X509PublicKey) or PEM;
 // its call site is reconfiguration_handler.cpp:332-338.  Key parsing here uses the host OpenSSL
 // (d2i_PUBKEY / PEM_read_bio_PUBKEY); secp256k1 batches of gpuMinBatch() items and more run on the
 // GPU, smaller ones and other curves on the host OpenSSL (the GPU path reproduces its verdicts).
+//
+// Signer: concord::util::crypto::ECDSASigner (crypto_utils.cpp:66-99), keyed from hex DER or PEM of an
+// EC private key.  secp256k1 keys sign with RFC 6979 nonces: sign() with the lane code of
+// csrc/ecdsa_sign.h built for the host, signBatch() on the GPU from gpuMinBatch() requests up, byte
+// for byte the same; other curves sign with the host OpenSSL.
 #include <openssl/bio.h>
 #include <openssl/bn.h>
 #include <openssl/core_names.h>
@@ -20,6 +25,9 @@
 #include <shared_mutex>
 #include <stdexcept>
 
+#include <openssl/crypto.h>
+
+#include "../../csrc/ecdsa_sign.h"  // the signing lane code, host build
 #include "cbft_hipcrypto.h"
 #include "hip_crypto.hpp"
 
@@ -40,6 +48,36 @@ EVP_PKEY* parseEcPublicKey(const std::string& s, KeyFormat fmt) {
   BIO_free(bio);
   return k;
 }
+
+EVP_PKEY* parseEcPrivateKey(const std::string& s, KeyFormat fmt) {
+  if (fmt == KeyFormat::HexaDecimalStrippedFormat) {
+    std::vector<uint8_t> der;
+    if (!fromHex(s, der) || der.empty()) return nullptr;
+    const unsigned char* p = der.data();
+    EVP_PKEY* k = d2i_AutoPrivateKey(nullptr, &p, (long)der.size());  // PKCS#8 or RFC 5915
+    OPENSSL_cleanse(der.data(), der.size());
+    return k;
+  }
+  BIO* bio = BIO_new_mem_buf(s.data(), (int)s.size());
+  if (!bio) return nullptr;
+  EVP_PKEY* k = PEM_read_bio_PrivateKey(bio, nullptr, nullptr, nullptr);
+  BIO_free(bio);
+  return k;
+}
+
+// G's comb table for the host build of the lane code (public data), built at the first sign()
+const uint32_t* hostCombTable() {
+  static std::once_flag once;
+  static std::vector<uint32_t> tbl;
+  std::call_once(once, [] {
+    tbl.assign(ECDSAS_TABLE_WORDS, 0);
+    for (int j = 0; j < ECDSAS_TABLE_LANES; j++) ecdsas_table_lane(tbl.data(), j);
+  });
+  return tbl.data();
+}
+
+std::atomic<uint64_t> g_sign_gpu_batches{0}, g_sign_gpu_items{0}, g_sign_host_items{0}, g_sign_gpu_errors{0};
+std::mutex g_sign_register_mu;
 
 [[noreturn]] void fail(const char* what, int rc) {
   throw std::runtime_error(std::string(what) + ": " + cbft_strerror(rc) + " " + cbft_last_error());
@@ -77,6 +115,16 @@ class EcdsaEngine {
     pubs_.insert(pubs_.end(), pub, pub + 64);
     index_.emplace(std::move(k), idx);
     return idx;
+  }
+
+  // Signer tables of HipECDSASigner::signBatch: one per signer object, loaded at its first GPU batch.
+  int loadSigner(const uint8_t priv[32], uint32_t* id) {
+    open();
+    return cbft_ecdsa_load_signers(ctx_, priv, 1, id);
+  }
+  void unloadSigner(uint32_t id) { (void)cbft_ecdsa_unload_signers(ctx_, id); }
+  int signBatch(uint32_t id, const uint8_t* blob, const uint64_t* off, const uint32_t* len, size_t n, uint8_t* sig) {
+    return cbft_ecdsa_sign_batch(ctx_, id, nullptr, blob, off, len, n, sig);
   }
 
   // one batch of 64-byte signatures; GPU failures become false verdicts and are counted
@@ -274,6 +322,151 @@ void HipECDSAVerifier::verifyBatch(const std::vector<VerifyRequest>& reqs, std::
   }
   engine->verifyNoThrow(kidx, sig, msg, off, len, bitmap);
   for (size_t j = 0; j < n; j++) out[pos[j]] = (bitmap[j >> 3] >> (j & 7)) & 1;
+}
+
+// ---- HipECDSASigner ------------------------------------------------------------------------------
+HipECDSASigner::HipECDSASigner(const std::string& str_priv_key, KeyFormat fmt) : key_str_(str_priv_key) {
+  std::memset(scalar_, 0, sizeof scalar_);
+  EVP_PKEY* k = parseEcPrivateKey(str_priv_key, fmt);
+  char group[80] = {0};
+  size_t glen = 0;
+  BIGNUM *order = nullptr, *d = nullptr;
+  bool ok = k && EVP_PKEY_get_base_id(k) == EVP_PKEY_EC &&
+            EVP_PKEY_get_utf8_string_param(k, OSSL_PKEY_PARAM_GROUP_NAME, group, sizeof group, &glen) == 1 &&
+            EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_EC_ORDER, &order) == 1 &&
+            EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_PRIV_KEY, &d) == 1;
+  if (ok) sig_len_ = 2u * (uint32_t)BN_num_bytes(order);
+  if (ok && std::strcmp(group, "secp256k1") == 0) {
+    ok = BN_bn2binpad(d, scalar_, 32) == 32;
+    gpu_capable_ = ok;
+  }
+  BN_free(order);
+  BN_clear_free(d);
+  if (!ok) {
+    EVP_PKEY_free(k);
+    OPENSSL_cleanse(scalar_, sizeof scalar_);
+    throw std::invalid_argument("HipECDSASigner: not an EC private key on a named curve");
+  }
+  pkey_ = k;
+}
+
+HipECDSASigner::~HipECDSASigner() {
+  if (engine_) engine_->unloadSigner(signer_table_);
+  OPENSSL_cleanse(scalar_, sizeof scalar_);
+  EVP_PKEY_free(static_cast<EVP_PKEY*>(pkey_));
+}
+
+size_t HipECDSASigner::gpuMinBatch() {
+  static const size_t v = [] {
+    const char* e = std::getenv("CBFT_ECDSA_SIGN_GPU_MIN");
+    const long long x = e ? std::atoll(e) : 0;
+    return x > 0 ? (size_t)x : (size_t)CBFT_ECDSA_SIGN_GPU_MIN_DEFAULT;
+  }();
+  return v;
+}
+
+std::string HipECDSASigner::getPubKeyHex() const {
+  unsigned char* der = nullptr;
+  const int n = i2d_PUBKEY(static_cast<EVP_PKEY*>(pkey_), &der);
+  if (n <= 0) throw std::runtime_error("HipECDSASigner: i2d_PUBKEY");
+  std::string hex = toHex(der, (size_t)n);
+  OPENSSL_free(der);
+  return hex;
+}
+
+std::string HipECDSASigner::sign(const std::string& data) {
+  std::string out(sig_len_, '\0');
+  if (gpu_capable_) {
+    if (data.size() > 0xFFFFFFFFull) throw std::runtime_error("HipECDSASigner: message too long");
+    // the lane code of the GPU kernels, built for the host: the same bytes, the same construction
+    uint32_t rec[ECDSAS_WORDS], h1[8], sig[16];
+    ecdsas_signer_lane(rec, scalar_, hostCombTable());
+    if (!rec[ECDSAS_OK]) throw std::runtime_error("HipECDSASigner: private scalar out of range");
+    ecdsa_sha256(h1, reinterpret_cast<const uint8_t*>(data.data()), (uint32_t)data.size());
+    ecdsas_sign_lane(sig, rec, h1, hostCombTable());
+    std::memcpy(&out[0], sig, 64);
+    OPENSSL_cleanse(rec, sizeof rec);
+    return out;
+  }
+  // another curve: EVP_DigestSign (SHA-256) on the host, DER -> r || s
+  EVP_MD_CTX* md = EVP_MD_CTX_new();
+  size_t dl = 0;
+  std::vector<unsigned char> der;
+  const unsigned char* m = reinterpret_cast<const unsigned char*>(data.data());
+  bool ok = md && EVP_DigestSignInit(md, nullptr, EVP_sha256(), nullptr, static_cast<EVP_PKEY*>(pkey_)) == 1 &&
+            EVP_DigestSign(md, nullptr, &dl, m, data.size()) == 1;
+  if (ok) {
+    der.resize(dl);
+    ok = EVP_DigestSign(md, der.data(), &dl, m, data.size()) == 1;
+  }
+  EVP_MD_CTX_free(md);
+  ECDSA_SIG* es = nullptr;
+  if (ok) {
+    const unsigned char* p = der.data();
+    es = d2i_ECDSA_SIG(nullptr, &p, (long)dl);
+  }
+  const int half = (int)(sig_len_ / 2);
+  ok = es && BN_bn2binpad(ECDSA_SIG_get0_r(es), reinterpret_cast<unsigned char*>(&out[0]), half) == half &&
+       BN_bn2binpad(ECDSA_SIG_get0_s(es), reinterpret_cast<unsigned char*>(&out[half]), half) == half;
+  ECDSA_SIG_free(es);
+  if (!ok) throw std::runtime_error("HipECDSASigner: EVP_DigestSign failed");
+  return out;
+}
+
+void HipECDSASigner::signBatch(const std::vector<SignRequest>& reqs) {
+  const size_t n = reqs.size();
+  if (n == 0) return;
+  bool onGpu = false;
+  if (gpu_capable_ && n >= gpuMinBatch()) {
+    try {
+      {
+        std::lock_guard<std::mutex> g(g_sign_register_mu);
+        if (!engine_) {
+          auto engine = EcdsaEngine::get();
+          uint32_t id = 0;
+          const int rc = engine->loadSigner(scalar_, &id);  // throws when the engine cannot be opened
+          if (rc != CBFT_OK) throw std::runtime_error("cbft_ecdsa_load_signers");
+          engine_ = std::move(engine);
+          signer_table_ = id;
+        }
+      }
+      size_t blob = 0;
+      bool fits = true;
+      for (const SignRequest& r : reqs) {
+        fits = fits && r.dataLength <= 0xFFFFFF00u;
+        blob += r.dataLength;
+      }
+      if (!fits) throw std::runtime_error("message too long for the GPU signer");
+      std::vector<uint8_t> msg(blob ? blob : 1), sig(n * 64);
+      std::vector<uint64_t> off(n);
+      std::vector<uint32_t> len(n);
+      size_t o = 0;
+      for (size_t i = 0; i < n; i++) {
+        off[i] = o;
+        len[i] = (uint32_t)reqs[i].dataLength;
+        if (reqs[i].dataLength) std::memcpy(&msg[o], reqs[i].data, reqs[i].dataLength);
+        o += reqs[i].dataLength;
+      }
+      const int rc = engine_->signBatch(signer_table_, msg.data(), off.data(), len.data(), n, sig.data());
+      if (rc != CBFT_OK) throw std::runtime_error("cbft_ecdsa_sign_batch");
+      for (size_t i = 0; i < n; i++) std::memcpy(reqs[i].outSig, &sig[64 * i], 64);
+      g_sign_gpu_batches++;
+      g_sign_gpu_items += n;
+      onGpu = true;
+    } catch (...) {
+      g_sign_gpu_errors++;
+    }
+  }
+  if (onGpu) return;
+  for (const SignRequest& r : reqs) {
+    const std::string s = sign(std::string(r.data, r.dataLength));
+    std::memcpy(r.outSig, s.data(), s.size());
+  }
+  g_sign_host_items += n;
+}
+
+SignStats ecdsaSignStats() {
+  return SignStats{g_sign_gpu_batches.load(), g_sign_gpu_items.load(), g_sign_host_items.load(), g_sign_gpu_errors.load()};
 }
 
 }  // namespace concord::hip

@@ -527,6 +527,50 @@ int cbft_ecdsa_verify_batch_device(cbft_ctx* ctx, uint32_t key_table_id, const u
  * (hash + verify). */
 int cbft_ecdsa_kernel_ms(cbft_ctx* ctx, float* out_ms);
 
+/* ECDSA secp256k1 / SHA-256 signing in batches: the batch form of concord::util::crypto::
+ * ECDSASigner (util/src/crypto_utils.cpp:66-99).  Signatures are r || s (64 bytes, big-endian),
+ * deterministic (tests/ecdsa_sign_ref.py restates them, tests/golden/ecdsa_sign_vectors.json pins
+ * them):
+ *   h1 = SHA-256(m);  e = h1 mod n;  k = the RFC 6979 section 3.2 nonce (HMAC-SHA-256 DRBG over
+ *   x || bits2octets(h1)): the first candidate with 1 <= k < n, r != 0 and s != 0;
+ *   r = x(k G) mod n;  s = k^-1 (e + r x) mod n, emitted as computed (no low-s rule).
+ * cbft_ecdsa_verify_batch, the reference's ECDSAVerifier and OpenSSL accept them.  The private key,
+ * the nonce and everything derived from them decide no branch, address or load on the GPU
+ * (DESIGN.md section 23); a signature never depends on the other items of its batch. */
+#define CBFT_ECDSA_PRIVATE_KEY_BYTES 32
+
+/* Load nkeys private keys (priv = nkeys x 32 bytes, big-endian): range check and public key
+ * Q = x G on the GPU, once.  A key that is 0 or >= n is accepted into the table as unusable
+ * (cbft_ecdsa_signer_status) and every signature under it is 64 zero bytes, which no verifier
+ * accepts.  nkeys > CBFT_ECDSA_MAX_KEYS is CBFT_E2BIG; nkeys = 0 is CBFT_EINVAL.  The keys cross in
+ * pinned staging that is wiped after the copy; the table and the nonce scratch are zeroed at unload
+ * and at cbft_close.
+ * Multi-GPU contexts keep signer tables on their first device. */
+int cbft_ecdsa_load_signers(cbft_ctx* ctx, const uint8_t* priv, uint32_t nkeys, uint32_t* out_signer_table_id);
+/* out_ok: nkeys bytes, 1 = the key is usable */
+int cbft_ecdsa_signer_status(cbft_ctx* ctx, uint32_t signer_table_id, uint8_t* out_ok);
+/* out_pub: nkeys x 64 bytes, X || Y big-endian as cbft_ecdsa_load_keys takes them; 64 zero bytes for
+ * an unusable key */
+int cbft_ecdsa_signer_public_keys(cbft_ctx* ctx, uint32_t signer_table_id, uint8_t* out_pub);
+int cbft_ecdsa_unload_signers(cbft_ctx* ctx, uint32_t signer_table_id);
+
+/* Sign n messages (message i = msg_blob[msg_off[i] .. + msg_len[i]), each at most CBFT_MAX_MSG_LEN
+ * bytes) with signer signer_idx[i] of the table (signer_idx = NULL: signer 0); out_sig = n x 64
+ * bytes.  n > CBFT_ECDSA_MAX_BATCH is CBFT_E2BIG; an unknown table, signer_idx[i] >= nkeys or a
+ * message over the cap is CBFT_EINVAL; n = 0 with a known table is CBFT_OK. */
+int cbft_ecdsa_sign_batch(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t* signer_idx,
+                          const uint8_t* msg_blob, const uint64_t* msg_off, const uint32_t* msg_len, size_t n,
+                          uint8_t* out_sig);
+/* Device-resident variant for n messages of one length (message i = d_msg[i * msg_len ..]),
+ * asynchronous on `stream` (nullptr = the context's own); d_sig: n x 64 bytes, 4-byte aligned;
+ * d_signer_idx may be null (signer 0); a signer index >= nkeys gives 64 zero bytes.  Calls on
+ * different streams share the nonce scratch and are ordered by the library.  Single-GPU contexts
+ * only (CBFT_EINVAL). */
+int cbft_ecdsa_sign_fixed_device(cbft_ctx* ctx, uint32_t signer_table_id, const uint32_t* d_signer_idx,
+                                 const uint8_t* d_msg, uint32_t msg_len, size_t n, uint8_t* d_sig, void* stream);
+/* With profiling enabled (cbft_set_profiling): the duration in ms of the last signing batch's kernels. */
+int cbft_ecdsa_sign_kernel_ms(cbft_ctx* ctx, float* out_ms);
+
 #ifdef __cplusplus
 }
 #endif
