@@ -12,8 +12,8 @@ ORACLE_LIB := oracle/libcbft_oracle.so
 # host SIMD emulation of the same source is exact).  Costs one v_mov_dpp per move.
 ROWFLAGS := -mllvm -amdgpu-dpp-combine=false
 
-.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test sanitize selftest
-all: lib oracle cpu host shim fe_row_shim bls_sign_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test selftest
+.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim bls_combine_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test sanitize selftest
+all: lib oracle cpu host shim fe_row_shim bls_sign_shim bls_combine_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test selftest
 
 lib: $(LIB)
 
@@ -72,6 +72,14 @@ $(CSRC)/bls_verify_batch.o: $(CSRC)/bls_verify_batch.hip $(CSRC)/bls_verify_batc
 $(CSRC)/cbft_bls_verify_batch.o: $(CSRC)/cbft_bls_verify_batch.cpp $(INTERNAL_DEPS) $(CSRC)/bls_verify_batch.h $(CSRC)/bls_kernels.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# BLS share combination in batches over many certificates: its own objects (the other BLS kernels are not touched)
+BLS_COMBINE_DEPS := $(CSRC)/bls_combine_batch.h $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
+$(CSRC)/bls_combine_batch.o: $(CSRC)/bls_combine_batch.hip $(BLS_COMBINE_DEPS)
+	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -c $< -o $@
+
+$(CSRC)/cbft_bls_combine_batch.o: $(CSRC)/cbft_bls_combine_batch.cpp $(INTERNAL_DEPS) $(BLS_COMBINE_DEPS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 # ECDSA secp256k1 verification: its own objects (no other kernel is touched)
 ECDSA_DEPS := $(CSRC)/ecdsa_verify.h $(CSRC)/fe_secp256k1.h $(CSRC)/sc_secp256k1.h $(CSRC)/ge_secp256k1.h $(CSRC)/safegcd30.h $(CSRC)/sha256.h
 $(CSRC)/ecdsa_verify.o: $(CSRC)/ecdsa_verify.hip $(ECDSA_DEPS)
@@ -91,7 +99,7 @@ $(CSRC)/cbft_ecdsa_sign.o: $(CSRC)/cbft_ecdsa_sign.cpp $(INTERNAL_DEPS) $(ECDSA_
 $(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(INTERNAL_DEPS) $(CSRC)/bls_kernels.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o $(CSRC)/ecdsa_sign.o $(CSRC)/cbft_ecdsa_sign.o
+$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/bls_combine_batch.o $(CSRC)/cbft_bls_combine_batch.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o $(CSRC)/ecdsa_sign.o $(CSRC)/cbft_ecdsa_sign.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle: $(ORACLE_LIB)
@@ -128,7 +136,7 @@ HOST_SRC := $(HOST_DIR)/src/hip_ed25519.cpp $(HOST_DIR)/src/hip_rsa.cpp $(HOST_D
 MIRROR_SRC := $(wildcard $(HOST_DIR)/ref_mirror/src/*.cpp)
 HOST_INC := -Iinclude -I$(HOST_DIR)/include -I$(HOST_DIR)/ref_mirror/include -DCBFT_WITH_CLIENT_KEYS_MAP
 HOST_HDRS := $(wildcard $(HOST_DIR)/include/*.hpp $(HOST_DIR)/include/threshsign/*.hpp $(HOST_DIR)/ref_mirror/include/*.hpp $(HOST_DIR)/ref_mirror/include/threshsign/*.h)
-host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_ecdsa_host tests/cpp/test_ecdsa_sign_host tools/host_bench
+host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_bls_combine_host tests/cpp/test_bls_combine_plan_san tests/cpp/test_ecdsa_host tests/cpp/test_ecdsa_sign_host tools/host_bench
 $(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB) $(ECDSA_SIGN_DEPS)
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN'
 tests/cpp/test_host: tests/cpp/test_host.cpp $(HOST_LIB)
@@ -145,6 +153,14 @@ tests/cpp/test_bls_sign_host: tests/cpp/test_bls_sign_host.cpp $(HOST_LIB)
 
 tests/cpp/test_bls_verify_host: tests/cpp/test_bls_verify_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+tests/cpp/test_bls_combine_host: tests/cpp/test_bls_combine_host.cpp $(HOST_LIB)
+	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+# the same test with the host sources compiled in under ASan + UBSan, for its --no-gpu mode (the planning of
+# combineBatch; run by tests/test_cpp_bls_combine_host.py as a stand-alone program, never loaded into python)
+tests/cpp/test_bls_combine_plan_san: tests/cpp/test_bls_combine_host.cpp $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB)
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $< $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_ecdsa_host: tests/cpp/test_ecdsa_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall -Wno-deprecated-declarations $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
@@ -170,6 +186,17 @@ BLS_SIGN_SHIM := tests/cpp/libbls_sign_shim.so
 bls_sign_shim: $(BLS_SIGN_SHIM)
 $(BLS_SIGN_SHIM): tests/cpp/bls_sign_shim.cpp $(CSRC)/bls_sign_batch.h $(CSRC)/bn254_*.h $(CSRC)/bls_ops.h $(CSRC)/sha256.h
 	g++ -O3 -funroll-loops -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $< -lpthread
+
+# host build of the batched BLS combination lane code (bls_combine_batch.h) for tests/test_bls_combine_batch_cpu.py,
+# and the same source as a stand-alone program under ASan + UBSan (run by that test, never loaded into python)
+BLS_COMBINE_SHIM := tests/cpp/libbls_combine_shim.so
+BLS_COMBINE_SHIM_SAN := tests/cpp/bls_combine_shim_san
+BLS_COMBINE_SHIM_DEPS := tests/cpp/bls_combine_shim.cpp $(CSRC)/bls_combine_batch.h $(CSRC)/bls_sign_batch.h $(CSRC)/bn254_*.h $(CSRC)/bls_ops.h $(CSRC)/sha256.h
+bls_combine_shim: $(BLS_COMBINE_SHIM) $(BLS_COMBINE_SHIM_SAN)
+$(BLS_COMBINE_SHIM): $(BLS_COMBINE_SHIM_DEPS)
+	g++ -O3 -funroll-loops -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $<
+$(BLS_COMBINE_SHIM_SAN): $(BLS_COMBINE_SHIM_DEPS)
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DBLS_COMBINE_SHIM_MAIN -I$(CSRC) -o $@ $<
 
 # host build of the row-parallel GF(2^255 - 19) code (fe25519_row.h) for tests/test_fe_row.py
 FE_ROW_SHIM := tests/cpp/libfe_row_shim.so
@@ -246,9 +273,10 @@ SIGN_SELFTEST := tests/hip/libsign_selftest.so
 RSA_SIGN_SELFTEST := tests/hip/librsa_sign_selftest.so
 BLS_SIGN_SELFTEST := tests/hip/libbls_sign_selftest.so
 BLS_VERIFY_SELFTEST := tests/hip/libbls_verify_selftest.so
+BLS_COMBINE_SELFTEST := tests/hip/libbls_combine_selftest.so
 FE25519_SELFTEST := tests/hip/libfe25519_selftest.so
 ECDSA_SIGN_SELFTEST := tests/hip/libecdsa_sign_selftest.so
-selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST) $(FE25519_SELFTEST) $(ECDSA_SIGN_SELFTEST)
+selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST) $(BLS_COMBINE_SELFTEST) $(FE25519_SELFTEST) $(ECDSA_SIGN_SELFTEST)
 # test-only device harness of the ECDSA signing lane code, one function per launch (tests/test_ecdsa_sign_gpu.py)
 $(ECDSA_SIGN_SELFTEST): tests/hip/ecdsa_sign_selftest.hip $(CSRC)/ecdsa_sign.hip $(ECDSA_SIGN_DEPS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
@@ -271,4 +299,8 @@ $(BLS_SIGN_SELFTEST): tests/hip/bls_sign_selftest.hip $(CSRC)/bls_sign_batch.h $
 # test-only device harness of the batched BLS verification: the product kernels timed stage by stage
 # (tools/bls_verify_bench.py)
 $(BLS_VERIFY_SELFTEST): tests/hip/bls_verify_selftest.hip $(CSRC)/bls_verify_batch.hip $(CSRC)/bls_verify_batch.h $(CSRC)/bls_sign_batch.h $(BLS_DEPS) $(LIB)
+	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -shared -o $@ $< -Lconcord-bft_amd -lcbft_hipcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+# test-only device harness of the batched BLS combination: the product kernels timed stage by stage, beside
+# the constant-time signing kernel on the same points (tools/bls_combine_bench.py)
+$(BLS_COMBINE_SELFTEST): tests/hip/bls_combine_selftest.hip $(CSRC)/bls_combine_batch.hip $(BLS_COMBINE_DEPS) $(LIB)
 	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -shared -o $@ $< -Lconcord-bft_amd -lcbft_hipcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'

@@ -141,6 +141,12 @@ ABI = [
     ("cbft_bls_verify_fixed_device", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32,
       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_bls_combine_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int,
+      ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_bls_combine_fixed_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_bls_combine_partial", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
       ctypes.c_void_p]),
@@ -804,6 +810,35 @@ class Context:
             self.handle, kid, ctypes.c_void_p(d_key_idx), ctypes.c_void_p(d_sig33), ctypes.c_void_p(d_msg), msg_len, m,
             ctypes.c_void_p(d_msg_of), n, ctypes.c_void_p(d_valid), ctypes.c_void_p(stream)),
             "cbft_bls_verify_fixed_device")
+
+    def bls_combine_batch(self, certs: Sequence[Sequence[bytes]], use=None, multisig: bool = False):
+        """Combines every certificate (a sequence of 37-byte shares) in one call: (sigs, status) with
+        sigs[c] the 33-byte combined signature and status[c] = 1, or 33 zero bytes and status[c] = 0
+        for a refused certificate.  use: one flag per share in certificate order (None: all used)."""
+        m = len(certs)
+        off = np.zeros(m + 1, dtype=np.uint64)
+        if m:
+            np.cumsum(np.array([len(c) for c in certs], dtype=np.uint64), out=off[1:])
+        flat = b"".join(s for c in certs for s in c)
+        assert len(flat) == 37 * int(off[m])
+        sh = np.frombuffer(flat or b"\0", dtype=np.uint8)
+        u = None if use is None else np.ascontiguousarray(np.asarray(use, dtype=np.uint8))
+        assert u is None or u.shape[0] == int(off[m])
+        out = np.zeros((max(1, m), 33), dtype=np.uint8)
+        status = np.zeros(max(1, m), dtype=np.uint8)
+        _check(self.lib.cbft_bls_combine_batch(self.handle, _ptr(sh), _ptr(off), m,
+                                               None if u is None or not u.size else _ptr(u), 1 if multisig else 0,
+                                               _ptr(out), _ptr(status)), "cbft_bls_combine_batch")
+        return [out[c].tobytes() for c in range(m)], status[:m]
+
+    def bls_combine_fixed_device(self, d_shares37: int, k: int, m: int, d_use: int, multisig: bool, d_out33: int,
+                                 d_status: int, stream: int = 0):
+        """k shares per certificate (share j of certificate c at d_shares37 + (c * k + j) * 37), signatures
+        to d_out33 (m x 33) and status bytes to d_status; raw device addresses (0 for d_use: all used)."""
+        _check(self.lib.cbft_bls_combine_fixed_device(
+            self.handle, ctypes.c_void_p(d_shares37), k, m, ctypes.c_void_p(d_use), 1 if multisig else 0,
+            ctypes.c_void_p(d_out33), ctypes.c_void_p(d_status), ctypes.c_void_p(stream)),
+            "cbft_bls_combine_fixed_device")
 
     def bls_public_key(self, sk: int) -> bytes:
         """sk * g2, 65 compressed bytes (the signer's share verification key)."""

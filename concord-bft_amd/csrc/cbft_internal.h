@@ -379,6 +379,11 @@ struct cbft_ctx {
     ScratchGuard scratch;  // hash points, decoded signatures, gate flags (public)
     DevBuf in, out;        // packed inputs / verdict bytes of a host-array batch
   } blsv;
+  // BLS share combination in batches (cbft_bls_combine_batch.cpp)
+  struct {
+    ScratchGuard scratch;  // decoded shares, coefficients, products, flags (public)
+    DevBuf in, out;        // shares | use | offsets, and signatures | status of a host-array batch
+  } blsc;
   // ECDSA secp256k1 verification (cbft_ecdsa.cpp)
   std::unordered_map<uint32_t, EcdsaKeyTable> ecdsa_tables;
   uint32_t next_ecdsa_id = 1;
@@ -411,6 +416,7 @@ void cbft_sign_release(cbft_ctx* c);
 void cbft_rsa_sign_release(cbft_ctx* c);
 void cbft_bls_sign_release(cbft_ctx* c);
 void cbft_bls_verify_batch_release(cbft_ctx* c);
+void cbft_bls_combine_batch_release(cbft_ctx* c);
 void cbft_ecdsa_release(cbft_ctx* c);
 void cbft_ecdsa_sign_release(cbft_ctx* c);
 // 32-byte big-endian BLS scalar -> 8 little-endian words reduced mod r, as cbft_bls_sign takes it;

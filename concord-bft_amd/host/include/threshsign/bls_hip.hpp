@@ -137,6 +137,8 @@ class BlsMultisigVerifier : public BlsThresholdVerifier {
   void verifyBatch(std::vector<BlsVerifyRequest>& requests) const override;
 };
 
+struct BlsCombineInput;
+
 // Accumulator state machine of ThresholdAccumulatorBase (pending / valid / invalid shares).
 class BlsAccumulatorBase : public IThresholdAccumulator {
  public:
@@ -147,8 +149,14 @@ class BlsAccumulatorBase : public IThresholdAccumulator {
   int getNumValidShares() const override;
   std::set<ShareID> getInvalidShareIds() const override { return invalid_; }
   int addNumById(ShareID signer, const uint8_t* share33);
+  // What getFullSignedData combines, for combineBatch: the valid shares as 37-byte records in id order,
+  // whether they are summed plainly (multisig), and the signer bitmap that follows the signature
+  // (k-of-n multisig: 256 bytes; otherwise empty)
+  void combineInput(BlsCombineInput& in) const;
+  const BlsThresholdVerifier& verifier() const { return v_; }
 
  protected:
+  virtual bool multisig() const = 0;
   using Share = std::array<uint8_t, 33>;
   bool hasExpectedDigest() const { return !digest_.empty(); }
   void verifyPendingShares();
@@ -170,6 +178,9 @@ class BlsThresholdAccumulator : public BlsAccumulatorBase {
   // sum lambda_i sigma_i over the valid shares -> 33 bytes (throws std::runtime_error if
   // threshSigLen < 33 or a share does not decode)
   void getFullSignedData(char* outThreshSig, int threshSigLen) override;
+
+ protected:
+  bool multisig() const override { return false; }
 };
 
 class BlsMultisigAccumulator : public BlsAccumulatorBase {
@@ -177,7 +188,56 @@ class BlsMultisigAccumulator : public BlsAccumulatorBase {
   using BlsAccumulatorBase::BlsAccumulatorBase;
   // sum sigma_i -> 33 bytes, || 256-byte signer bitmap when reqSigners != numSigners
   void getFullSignedData(char* outThreshSig, int threshSigLen) override;
+
+ protected:
+  bool multisig() const override { return true; }
 };
+
+// One certificate to combine in combineBatch: out receives what acc->getFullSignedData(out, outLen)
+// writes (33 bytes, 33 + 256 for a k-of-n multisig accumulator); ok = false where that call would throw
+// (out too short, a share that does not decode), and out is then left as it was.
+struct BlsCombineRequest {
+  IThresholdAccumulator* acc;
+  char* out;
+  int outLen;
+  bool ok;
+};
+
+// An accumulator's state as combineBatch reads it (BlsAccumulatorBase::combineInput); usable = false
+// for a null pointer or an accumulator of another implementation.
+struct BlsCombineInput {
+  bool usable = false;
+  bool multisig = false;
+  std::vector<uint8_t> records;  // 37 bytes per valid share, id order
+  std::vector<uint8_t> signers;  // what follows the signature in out
+};
+
+// What combineBatch hands to ONE cbft_bls_combine_batch call: the requests that pass the buffer checks
+// and hold at least one share (certificate j is request item[j], its shares certOff[j] .. certOff[j + 1]
+// of shares37).  Built without the GPU.
+struct BlsCombinePlan {
+  std::vector<uint32_t> item;
+  std::vector<uint64_t> certOff;
+  std::vector<uint8_t> shares37;
+  bool multisig = false;
+};
+
+// Smallest combineBatch that runs as ONE cbft_bls_combine_batch call ($CBFT_BLS_COMBINE_BATCH_MIN
+// overrides); smaller ones loop getFullSignedData (cbft_bls_combine).  The measured crossover of one
+// batch call against m lone calls at k = 5, host arrays in to host arrays out.
+#define CBFT_BLS_COMBINE_BATCH_MIN_DEFAULT 5
+
+// The batch form of getFullSignedData over the accumulators of ONE verifier (a collector's window of
+// sequence numbers, the certificates of a view change): every request's ok is set and every out that
+// is ok holds the bytes the lone call writes.  combineBatchMin() requests or more run as one
+// cbft_bls_combine_batch call, fewer as lone calls; the outputs are the same.  Throws
+// std::invalid_argument when the accumulators are of different verifiers.
+void combineBatch(std::vector<BlsCombineRequest>& requests);
+size_t combineBatchMin();
+// Packing, offsets and refusals: requests that need no device (no buffer, a short one, an unusable
+// accumulator: ok = false; no valid share: the identity, ok = true) are answered here, the others packed
+// for one call.  in[i] is request i's accumulator.  Throws std::invalid_argument on mixed kinds.
+void planCombine(const std::vector<BlsCombineInput>& in, std::vector<BlsCombineRequest>& requests, BlsCombinePlan& plan);
 
 // One share to sign in BlsThresholdSigner::signBatch: out receives 37 bytes (outLen >= 37).
 struct BlsSignRequest {

@@ -415,6 +415,94 @@ void BlsMultisigAccumulator::getFullSignedData(char* out, int len) {
   if (vec) validBits_.toBytes(reinterpret_cast<unsigned char*>(out) + 33, vec);
 }
 
+// ------------------------------------------------------------------------------ batched combination
+void BlsAccumulatorBase::combineInput(BlsCombineInput& in) const {
+  in.usable = true;
+  in.multisig = multisig();
+  in.records = validRecords();
+  in.signers.clear();
+  if (in.multisig && req_ != num_) {
+    in.signers.resize((size_t)VectorOfShares::getByteCount());
+    validBits_.toBytes(in.signers.data(), (int)in.signers.size());
+  }
+}
+
+size_t combineBatchMin() {
+  static const size_t v = [] {
+    const char* e = std::getenv("CBFT_BLS_COMBINE_BATCH_MIN");
+    const long long x = e ? std::atoll(e) : 0;
+    return x > 0 ? (size_t)x : (size_t)CBFT_BLS_COMBINE_BATCH_MIN_DEFAULT;
+  }();
+  return v;
+}
+
+void planCombine(const std::vector<BlsCombineInput>& in, std::vector<BlsCombineRequest>& requests, BlsCombinePlan& plan) {
+  if (in.size() != requests.size()) throw std::invalid_argument("planCombine: one input per request");
+  plan = BlsCombinePlan();
+  plan.certOff.push_back(0);
+  bool kindKnown = false;
+  for (size_t i = 0; i < requests.size(); i++) {
+    BlsCombineRequest& r = requests[i];
+    const BlsCombineInput& a = in[i];
+    r.ok = false;
+    if (!a.usable) continue;
+    if (kindKnown && a.multisig != plan.multisig) throw std::invalid_argument("combineBatch: accumulators of two kinds");
+    plan.multisig = a.multisig;
+    kindKnown = true;
+    if (a.records.size() % 37 != 0) throw std::invalid_argument("planCombine: records are 37 bytes each");
+    if (!r.out || r.outLen < 0 || (size_t)r.outLen < 33 + a.signers.size()) continue;  // getFullSignedData throws
+    if (a.records.empty()) {  // the identity (G1T::Identity(), BlsThresholdAccumulator.cpp:34)
+      std::memset(r.out, 0, 33);
+      if (!a.signers.empty()) std::memcpy(r.out + 33, a.signers.data(), a.signers.size());
+      r.ok = true;
+      continue;
+    }
+    plan.item.push_back((uint32_t)i);
+    plan.shares37.insert(plan.shares37.end(), a.records.begin(), a.records.end());
+    plan.certOff.push_back(plan.shares37.size() / 37);
+  }
+}
+
+void combineBatch(std::vector<BlsCombineRequest>& requests) {
+  const BlsThresholdVerifier* v = nullptr;
+  std::vector<BlsCombineInput> in(requests.size());
+  for (size_t i = 0; i < requests.size(); i++) {
+    const auto* a = dynamic_cast<const BlsAccumulatorBase*>(requests[i].acc);
+    if (!a) continue;
+    if (v && v != &a->verifier()) throw std::invalid_argument("combineBatch: accumulators of different verifiers");
+    v = &a->verifier();
+    if (requests.size() >= combineBatchMin()) a->combineInput(in[i]);
+  }
+  if (requests.size() < combineBatchMin()) {
+    for (BlsCombineRequest& r : requests) {
+      r.ok = false;
+      if (!dynamic_cast<const BlsAccumulatorBase*>(r.acc)) continue;
+      try {
+        r.acc->getFullSignedData(r.out, r.outLen);
+        r.ok = true;
+      } catch (const std::runtime_error&) {
+      }
+    }
+    return;
+  }
+  BlsCombinePlan p;
+  planCombine(in, requests, p);
+  const size_t m = p.item.size();
+  if (m == 0) return;
+  std::vector<uint8_t> sig(33 * m), status(m);
+  check(cbft_bls_combine_batch(v->engine()->ctx(), p.shares37.data(), p.certOff.data(), m, nullptr, p.multisig ? 1 : 0,
+                               sig.data(), status.data()),
+        "cbft_bls_combine_batch");
+  for (size_t j = 0; j < m; j++) {
+    if (!status[j]) continue;
+    BlsCombineRequest& r = requests[p.item[j]];
+    std::memcpy(r.out, &sig[33 * j], 33);
+    const std::vector<uint8_t>& tail = in[p.item[j]].signers;
+    if (!tail.empty()) std::memcpy(r.out + 33, tail.data(), tail.size());
+    r.ok = true;
+  }
+}
+
 // ------------------------------------------------------------------------------ signer
 BlsThresholdSigner::BlsThresholdSigner(ShareID id, const std::string& secretKeyDecimal, const std::string& vkHex)
     : id_(id), sk_(secretKeyDecimal), vk_(vkHex.empty() ? BlsPublicKey() : BlsPublicKey(vkHex)) {

@@ -486,6 +486,39 @@ int cbft_bls_verify_fixed_device(cbft_ctx* ctx, uint32_t keyset, const uint32_t*
                                  const uint8_t* d_msg, uint32_t msg_len, size_t m, const uint32_t* d_msg_of, size_t n,
                                  uint8_t* d_valid, void* stream);
 
+/* ---- Batched share combination over many certificates: the step between cbft_bls_sign_batch and
+ * cbft_bls_verify_batch.  Certificate c owns the 37-byte shares cert_off[c] .. cert_off[c + 1] of
+ * shares37 (m + 1 non-decreasing offsets, counted in shares); use (nullable) holds one byte per
+ * share, indexed like shares37: a share with use[j] == 0 is not decoded, not range-checked and not
+ * part of the Lagrange set (null: every share is used).  use takes the verdict bytes of
+ * cbft_bls_verify_fixed_device as they are: the fallback arm of the SignaturesProcessingJob policy
+ * over a whole window of certificates.
+ *
+ * Per certificate, over its used shares: status[c] = 1 and out33[c] = the combined signature, byte
+ * for byte what cbft_bls_combine returns for exactly those shares (an infinite share counts as the
+ * point it is, an infinite sum is 33 zero bytes with status 1).  status[c] = 0 and out33[c] = 33
+ * zero bytes when a used share does not decode, an id is outside [1, 2048], two used shares carry
+ * the same id, or no share is used (an empty certificate included).  A refused certificate never
+ * affects its neighbours.  33 zero bytes with status 0 are also what a refused certificate hands to
+ * the next stage: they decode as the point at infinity, which verifies under no usable key, so
+ * cbft_bls_verify_fixed_device gives such a certificate verdict 0; read status to tell a refusal
+ * from an infinite sum.
+ *
+ * Host arrays, blocking.  CBFT_EINVAL before anything is launched, outputs untouched: a null
+ * pointer (use excepted), cert_off decreasing somewhere, or a certificate of more than 2048 shares.
+ * m = 0 is CBFT_OK.  Up to 2^26 shares per call (CBFT_E2BIG).  On a multi-GPU context each device
+ * combines a contiguous slice of the certificates. */
+int cbft_bls_combine_batch(cbft_ctx* ctx, const uint8_t* shares37, const uint64_t* cert_off, size_t m,
+                           const uint8_t* use, int multisig, uint8_t* out33, uint8_t* status);
+/* Device-resident form with k shares per certificate: share j of certificate c at
+ * d_shares37 + (c * k + j) * 37, d_use (nullable) one byte per share, d_out33 m x 33, d_status m.
+ * Asynchronous on `stream` (nullptr = the context's own stream).  k > 2048 is CBFT_EINVAL, more than
+ * 2^26 shares CBFT_E2BIG.  Calls on different streams share the batch scratch and are ordered by the
+ * library.  Single-GPU contexts only. */
+int cbft_bls_combine_fixed_device(cbft_ctx* ctx, const uint8_t* d_shares37, uint32_t k, size_t m,
+                                  const uint8_t* d_use, int multisig, uint8_t* d_out33, uint8_t* d_status,
+                                  void* stream);
+
 /* ------------------------------------------------------- ECDSA secp256k1 / SHA-256 ------------
  * Replaces concord::util::crypto::ECDSAVerifier (util/src/crypto_utils.cpp:34-64,231-236), i.e.
  * Crypto++ ECDSA<ECP, SHA256> on its default curve secp256k1.  Verdicts are those of OpenSSL 3.0.2
