@@ -35,7 +35,7 @@ $(CSRC)/bls_pairing.o: $(CSRC)/bls_pairing.hip $(BLS_DEPS)
 $(CSRC)/bls_msm_row.o: $(CSRC)/bls_msm_row.hip $(BLS_DEPS) $(CSRC)/bls_glv.h
 	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -c $< -o $@
 
-$(CSRC)/bls_keys.o: $(CSRC)/bls_keys.hip $(BLS_DEPS)
+$(CSRC)/bls_keys.o: $(CSRC)/bls_keys.hip $(CSRC)/bls_g2_shared.h $(BLS_DEPS)
 	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -c $< -o $@
 
 $(CSRC)/rsa_verify.o: $(CSRC)/rsa_verify.hip $(CSRC)/rsa_verify.h $(CSRC)/sha256.h
@@ -80,6 +80,14 @@ $(CSRC)/bls_combine_batch.o: $(CSRC)/bls_combine_batch.hip $(BLS_COMBINE_DEPS)
 $(CSRC)/cbft_bls_combine_batch.o: $(CSRC)/cbft_bls_combine_batch.cpp $(INTERNAL_DEPS) $(BLS_COMBINE_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# BLS multisig verification in batches over many signer sets: its own objects (the other BLS kernels are not touched)
+BLS_MULTISIG_DEPS := $(CSRC)/bls_multisig_batch.h $(CSRC)/bls_verify_batch.h $(CSRC)/bls_g2_shared.h $(BLS_DEPS)
+$(CSRC)/bls_multisig_batch.o: $(CSRC)/bls_multisig_batch.hip $(BLS_MULTISIG_DEPS)
+	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -c $< -o $@
+
+$(CSRC)/cbft_bls_multisig_batch.o: $(CSRC)/cbft_bls_multisig_batch.cpp $(INTERNAL_DEPS) $(BLS_MULTISIG_DEPS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 # ECDSA secp256k1 verification: its own objects (no other kernel is touched)
 ECDSA_DEPS := $(CSRC)/ecdsa_verify.h $(CSRC)/fe_secp256k1.h $(CSRC)/sc_secp256k1.h $(CSRC)/ge_secp256k1.h $(CSRC)/safegcd30.h $(CSRC)/sha256.h
 $(CSRC)/ecdsa_verify.o: $(CSRC)/ecdsa_verify.hip $(ECDSA_DEPS)
@@ -99,7 +107,7 @@ $(CSRC)/cbft_ecdsa_sign.o: $(CSRC)/cbft_ecdsa_sign.cpp $(INTERNAL_DEPS) $(ECDSA_
 $(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(INTERNAL_DEPS) $(CSRC)/bls_kernels.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/bls_combine_batch.o $(CSRC)/cbft_bls_combine_batch.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o $(CSRC)/ecdsa_sign.o $(CSRC)/cbft_ecdsa_sign.o
+$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/bls_combine_batch.o $(CSRC)/cbft_bls_combine_batch.o $(CSRC)/bls_multisig_batch.o $(CSRC)/cbft_bls_multisig_batch.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o $(CSRC)/ecdsa_sign.o $(CSRC)/cbft_ecdsa_sign.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle: $(ORACLE_LIB)
@@ -136,7 +144,7 @@ HOST_SRC := $(HOST_DIR)/src/hip_ed25519.cpp $(HOST_DIR)/src/hip_rsa.cpp $(HOST_D
 MIRROR_SRC := $(wildcard $(HOST_DIR)/ref_mirror/src/*.cpp)
 HOST_INC := -Iinclude -I$(HOST_DIR)/include -I$(HOST_DIR)/ref_mirror/include -DCBFT_WITH_CLIENT_KEYS_MAP
 HOST_HDRS := $(wildcard $(HOST_DIR)/include/*.hpp $(HOST_DIR)/include/threshsign/*.hpp $(HOST_DIR)/ref_mirror/include/*.hpp $(HOST_DIR)/ref_mirror/include/threshsign/*.h)
-host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_bls_combine_host tests/cpp/test_bls_combine_plan_san tests/cpp/test_ecdsa_host tests/cpp/test_ecdsa_sign_host tools/host_bench
+host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_bls_combine_host tests/cpp/test_bls_combine_plan_san tests/cpp/test_bls_multisig_host tests/cpp/test_bls_multisig_plan_san tests/cpp/test_ecdsa_host tests/cpp/test_ecdsa_sign_host tools/host_bench
 $(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB) $(ECDSA_SIGN_DEPS)
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN'
 tests/cpp/test_host: tests/cpp/test_host.cpp $(HOST_LIB)
@@ -160,6 +168,14 @@ tests/cpp/test_bls_combine_host: tests/cpp/test_bls_combine_host.cpp $(HOST_LIB)
 # the same test with the host sources compiled in under ASan + UBSan, for its --no-gpu mode (the planning of
 # combineBatch; run by tests/test_cpp_bls_combine_host.py as a stand-alone program, never loaded into python)
 tests/cpp/test_bls_combine_plan_san: tests/cpp/test_bls_combine_host.cpp $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB)
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $< $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+tests/cpp/test_bls_multisig_host: tests/cpp/test_bls_multisig_host.cpp $(HOST_LIB)
+	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+# the same test with the host sources compiled in under ASan + UBSan, for its --no-gpu mode (the planning of the
+# multisig verifyBatch; run by tests/test_cpp_bls_multisig_host.py as a stand-alone program, never loaded into python)
+tests/cpp/test_bls_multisig_plan_san: tests/cpp/test_bls_multisig_host.cpp $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB)
 	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $< $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_ecdsa_host: tests/cpp/test_ecdsa_host.cpp $(HOST_LIB)

@@ -147,6 +147,16 @@ ABI = [
     ("cbft_bls_combine_fixed_device", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int,
       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_bls_verify_multisig_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+      ctypes.c_void_p]),
+    ("cbft_bls_verify_multisig_fixed_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+      ctypes.c_void_p]),
+    ("cbft_bls_sum_keys_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_bls_combine_partial", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
       ctypes.c_void_p]),
@@ -839,6 +849,47 @@ class Context:
             self.handle, ctypes.c_void_p(d_shares37), k, m, ctypes.c_void_p(d_use), 1 if multisig else 0,
             ctypes.c_void_p(d_out33), ctypes.c_void_p(d_status), ctypes.c_void_p(stream)),
             "cbft_bls_combine_fixed_device")
+
+    def bls_verify_multisig_batch(self, kid: int, sigs: Sequence[bytes], msgs: Sequence[bytes],
+                                  sets: Sequence[bytes], set_of=None, msg_of=None) -> np.ndarray:
+        """Verdicts (n,) bool of n independent multisig checks: sigs[i] (33 bytes) on msgs[msg_of[i]] (None:
+        msgs[i], needs len(msgs) == len(sigs)) under the sum of the keys that the 256-byte signer bitmap
+        sets[set_of[i]] selects (None: sets[i], needs len(sets) == len(sigs))."""
+        n, m, s = len(sigs), len(msgs), len(sets)
+        assert all(len(x) == 33 for x in sigs) and all(len(b) == 256 for b in sets)
+        blob, offs, lens = pack_messages(msgs)
+        sig = np.frombuffer(b"".join(sigs), dtype=np.uint8) if n else np.zeros(1, dtype=np.uint8)
+        bm = np.frombuffer(b"".join(sets), dtype=np.uint8) if s else np.zeros(1, dtype=np.uint8)
+        sof = None if set_of is None else np.ascontiguousarray(np.asarray(set_of, dtype=np.uint32))
+        mof = None if msg_of is None else np.ascontiguousarray(np.asarray(msg_of, dtype=np.uint32))
+        assert (sof is None or sof.shape[0] == n) and (mof is None or mof.shape[0] == n)
+        out = np.zeros(max(1, (n + 7) // 8), dtype=np.uint8)
+        _check(self.lib.cbft_bls_verify_multisig_batch(
+            self.handle, kid, _ptr(bm), s, None if sof is None else _ptr(sof), _ptr(sig), _ptr(blob), _ptr(offs),
+            _ptr(lens), m, None if mof is None else _ptr(mof), n, _ptr(out)), "cbft_bls_verify_multisig_batch")
+        return bitmap_to_bools(out.tobytes(), n)
+
+    def bls_verify_multisig_fixed_device(self, kid: int, d_signers256: int, s: int, d_set_of: int, d_sig33: int,
+                                         d_msg: int, msg_len: int, m: int, d_msg_of: int, n: int, d_valid: int,
+                                         stream: int = 0):
+        """s signer bitmaps at d_signers256, fixed-length messages (message j at d_msg + j * msg_len), verdict
+        bytes to d_valid; raw device addresses (0 for d_set_of: item i uses set i; 0 for d_msg_of: item i
+        signs message i)."""
+        _check(self.lib.cbft_bls_verify_multisig_fixed_device(
+            self.handle, kid, ctypes.c_void_p(d_signers256), s, ctypes.c_void_p(d_set_of), ctypes.c_void_p(d_sig33),
+            ctypes.c_void_p(d_msg), msg_len, m, ctypes.c_void_p(d_msg_of), n, ctypes.c_void_p(d_valid),
+            ctypes.c_void_p(stream)), "cbft_bls_verify_multisig_fixed_device")
+
+    def bls_sum_keys_batch(self, kid: int, sets: Sequence[bytes]):
+        """(sums, ok): sums[j] the 65 bytes and ok[j] the status that bls_sum_keys gives for bitmap sets[j]."""
+        s = len(sets)
+        assert all(len(b) == 256 for b in sets)
+        bm = np.frombuffer(b"".join(sets), dtype=np.uint8) if s else np.zeros(1, dtype=np.uint8)
+        out = np.zeros((max(1, s), 65), dtype=np.uint8)
+        ok = np.zeros(max(1, s), dtype=np.uint8)
+        _check(self.lib.cbft_bls_sum_keys_batch(self.handle, kid, _ptr(bm), s, _ptr(out), _ptr(ok)),
+               "cbft_bls_sum_keys_batch")
+        return [out[j].tobytes() for j in range(s)], ok[:s]
 
     def bls_public_key(self, sk: int) -> bytes:
         """sk * g2, 65 compressed bytes (the signer's share verification key)."""

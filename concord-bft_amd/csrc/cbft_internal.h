@@ -384,6 +384,11 @@ struct cbft_ctx {
     ScratchGuard scratch;  // decoded shares, coefficients, products, flags (public)
     DevBuf in, out;        // shares | use | offsets, and signatures | status of a host-array batch
   } blsc;
+  // BLS multisig verification in batches (cbft_bls_multisig_batch.cpp)
+  struct {
+    ScratchGuard scratch;  // the verification's scratch, then per set: lines, affine sum, partials, flag (public)
+    DevBuf in, sets, out;  // packed inputs, signer bitmaps / verdict bytes (or key sums) of a host-array batch
+  } blsm;
   // ECDSA secp256k1 verification (cbft_ecdsa.cpp)
   std::unordered_map<uint32_t, EcdsaKeyTable> ecdsa_tables;
   uint32_t next_ecdsa_id = 1;
@@ -417,6 +422,7 @@ void cbft_rsa_sign_release(cbft_ctx* c);
 void cbft_bls_sign_release(cbft_ctx* c);
 void cbft_bls_verify_batch_release(cbft_ctx* c);
 void cbft_bls_combine_batch_release(cbft_ctx* c);
+void cbft_bls_multisig_batch_release(cbft_ctx* c);
 void cbft_ecdsa_release(cbft_ctx* c);
 void cbft_ecdsa_sign_release(cbft_ctx* c);
 // 32-byte big-endian BLS scalar -> 8 little-endian words reduced mod r, as cbft_bls_sign takes it;

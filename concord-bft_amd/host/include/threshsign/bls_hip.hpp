@@ -122,6 +122,22 @@ class BlsThresholdVerifier : public IThresholdVerifier {
   uint32_t keyset_ = 0;
 };
 
+// What the k-of-n verifyBatch hands to ONE cbft_bls_verify_multisig_batch call: the signer == 0 requests
+// that pass verify()'s host-side rules (length, at least reqSigners signers, no id above numSigners; item j
+// is request item[j]), identical signer bitmaps stored once (setOf) and identical messages stored once
+// (msgOf).  Built without the GPU.
+struct BlsMultisigPlan {
+  std::vector<uint32_t> item, setOf, msgOf, msgLen;
+  std::vector<uint64_t> msgOff;
+  std::vector<uint8_t> sig33, sets, blob;
+};
+
+// Smallest number of k-of-n certificates that BlsMultisigVerifier::verifyBatch runs as ONE
+// cbft_bls_verify_multisig_batch call ($CBFT_BLS_MULTISIG_BATCH_MIN overrides); fewer loop
+// cbft_bls_verify_multisig.  The measured crossover of one batch call against n lone calls, host arrays in
+// to verdicts out.
+#define CBFT_BLS_MULTISIG_BATCH_MIN_DEFAULT 3
+
 class BlsMultisigVerifier : public BlsThresholdVerifier {
  public:
   // PK is the sum of the vk_i (BlsMultisigVerifier.cpp:33-38); pkHex is not needed.
@@ -132,9 +148,15 @@ class BlsMultisigVerifier : public BlsThresholdVerifier {
   // throws std::runtime_error on a wrong-size k-of-n signature (BlsMultisigVerifier.cpp:77)
   bool verify(const char* msg, int msgLen, const char* sig, int sigLen) const override;
   // n-of-n: 33-byte signatures go through the batch under the summed key.  k-of-n: a signature carries
-  // its signer bitmap and its own key sum, so signer == 0 requests fall back to verify() one by one
-  // (ok = false instead of verify()'s exception for a wrong size); shares still run as one batch.
+  // its signer bitmap and is checked under its own key sum: multisigBatchMin() such requests or more run as
+  // one cbft_bls_verify_multisig_batch call, fewer through verify() one by one; the verdicts are the same
+  // (ok = false instead of verify()'s exception for a wrong size).  Shares still run as one batch.
   void verifyBatch(std::vector<BlsVerifyRequest>& requests) const override;
+  static size_t multisigBatchMin();
+  // the signer == 0 requests that need a pairing, packed for one call, with ok = false for all of them;
+  // requests with signer != 0 are left alone
+  static void planMultisigBatch(std::vector<BlsVerifyRequest>& requests, NumSharesType reqSigners,
+                                NumSharesType numSigners, BlsMultisigPlan& plan);
 };
 
 struct BlsCombineInput;

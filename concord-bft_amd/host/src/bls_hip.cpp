@@ -257,19 +257,84 @@ bool BlsMultisigVerifier::verify(const char* msg, int msgLen, const char* sig, i
   return ok != 0;
 }
 
-void BlsMultisigVerifier::verifyBatch(std::vector<BlsVerifyRequest>& requests) const {
-  if (req_ == num_) return BlsThresholdVerifier::verifyBatch(requests);
-  // the shares as one batch; each k-of-n signature under its own key sum, by verify()
-  std::vector<BlsVerifyRequest> shares;
-  std::vector<size_t> at;
+size_t BlsMultisigVerifier::multisigBatchMin() {
+  static const size_t v = [] {
+    const char* e = std::getenv("CBFT_BLS_MULTISIG_BATCH_MIN");
+    const long long x = e ? std::atoll(e) : 0;
+    return x > 0 ? (size_t)x : (size_t)CBFT_BLS_MULTISIG_BATCH_MIN_DEFAULT;
+  }();
+  return v;
+}
+
+void BlsMultisigVerifier::planMultisigBatch(std::vector<BlsVerifyRequest>& requests, NumSharesType reqSigners,
+                                            NumSharesType numSigners, BlsMultisigPlan& plan) {
+  plan = BlsMultisigPlan();
+  const size_t setLen = (size_t)VectorOfShares::getByteCount();
+  std::unordered_map<std::string, uint32_t> seenMsg, seenSet;  // bytes -> index in the plan
   for (size_t i = 0; i < requests.size(); i++) {
     BlsVerifyRequest& r = requests[i];
-    if (r.signer != 0) {
-      shares.push_back(r);
-      at.push_back(i);
-    } else {
-      r.ok = r.sigLen == requiredLengthForSignedData() && verify(r.msg, r.msgLen, r.sig, r.sigLen);
+    if (r.signer != 0) continue;
+    r.ok = false;
+    if (r.sigLen != 33 + (int)setLen || !r.msg || r.msgLen < 0 || !r.sig) continue;
+    const uint8_t* s = reinterpret_cast<const uint8_t*>(r.sig);
+    const uint8_t* bm = s + 33;
+    // verify()'s rules: at least reqSigners signers, none above numSigners
+    size_t count = 0;
+    bool above = false;
+    for (size_t q = 0; q < setLen; q++)
+      for (int t = 0; t < 8; t++)
+        if ((bm[q] >> t) & 1) {
+          count++;
+          above = above || 8 * q + t + 1 > (size_t)numSigners;
+        }
+    if (count < (size_t)reqSigners || above) continue;
+    std::string mkey(r.msg, (size_t)r.msgLen);
+    auto mi = seenMsg.find(mkey);
+    if (mi == seenMsg.end()) {
+      mi = seenMsg.emplace(std::move(mkey), (uint32_t)plan.msgLen.size()).first;
+      plan.msgOff.push_back(plan.blob.size());
+      plan.msgLen.push_back((uint32_t)r.msgLen);
+      plan.blob.insert(plan.blob.end(), r.msg, r.msg + r.msgLen);
     }
+    std::string skey(reinterpret_cast<const char*>(bm), setLen);
+    auto si = seenSet.find(skey);
+    if (si == seenSet.end()) {
+      si = seenSet.emplace(std::move(skey), (uint32_t)(plan.sets.size() / setLen)).first;
+      plan.sets.insert(plan.sets.end(), bm, bm + setLen);
+    }
+    plan.item.push_back((uint32_t)i);
+    plan.setOf.push_back(si->second);
+    plan.msgOf.push_back(mi->second);
+    plan.sig33.insert(plan.sig33.end(), s, s + 33);
+  }
+}
+
+void BlsMultisigVerifier::verifyBatch(std::vector<BlsVerifyRequest>& requests) const {
+  if (req_ == num_) return BlsThresholdVerifier::verifyBatch(requests);
+  // the shares as one batch; the k-of-n signatures, each under its own key sum, as another
+  std::vector<BlsVerifyRequest> shares;
+  std::vector<size_t> at;
+  for (size_t i = 0; i < requests.size(); i++)
+    if (requests[i].signer != 0) {
+      shares.push_back(requests[i]);
+      at.push_back(i);
+    }
+  BlsMultisigPlan p;
+  planMultisigBatch(requests, req_, num_, p);
+  const size_t n = p.item.size();
+  if (n && n < multisigBatchMin()) {
+    for (size_t j = 0; j < n; j++) {
+      BlsVerifyRequest& r = requests[p.item[j]];
+      r.ok = verify(r.msg, r.msgLen, r.sig, r.sigLen);
+    }
+  } else if (n) {
+    if (p.blob.empty()) p.blob.push_back(0);
+    std::vector<uint8_t> bits((n + 7) / 8);
+    check(cbft_bls_verify_multisig_batch(engine_->ctx(), keyset_, p.sets.data(), p.sets.size() / 256, p.setOf.data(),
+                                         p.sig33.data(), p.blob.data(), p.msgOff.data(), p.msgLen.data(),
+                                         p.msgLen.size(), p.msgOf.data(), n, bits.data()),
+          "cbft_bls_verify_multisig_batch");
+    for (size_t j = 0; j < n; j++) requests[p.item[j]].ok = ((bits[j >> 3] >> (j & 7)) & 1) != 0;
   }
   BlsThresholdVerifier::verifyBatch(shares);
   for (size_t j = 0; j < at.size(); j++) requests[at[j]].ok = shares[j].ok;

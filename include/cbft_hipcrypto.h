@@ -519,6 +519,49 @@ int cbft_bls_combine_fixed_device(cbft_ctx* ctx, const uint8_t* d_shares37, uint
                                   const uint8_t* d_use, int multisig, uint8_t* d_out33, uint8_t* d_status,
                                   void* stream);
 
+/* ---- Batched multisig verification over many signer sets: the step after cbft_bls_combine_batch
+ * (multisig = 1) for k-of-n multisig keys, whose certificate is sigma33 || 256-byte signer bitmap
+ * checked under PK = sum of vk_id over the bitmap.  signers256 holds s bitmaps of 256 bytes (bit
+ * id - 1, LSB first, as VectorOfShares); item i is checked under the key sum of set set_of[i]
+ * (nullptr: set i, which needs s == n) on message msg_of[i] of the m messages (nullptr: message i,
+ * which needs m == n).  Every set is summed once, however many items name it; identical bitmaps in
+ * different slots are not merged (the caller may).
+ *
+ * Item i is valid iff cbft_bls_verify_multisig(ctx, keyset, msg[msg_of[i]], sig33[i],
+ * signers256[set_of[i]]) says so on that item alone; verdicts are exact, per item (no random linear
+ * combination).  As there: bits for ids above n_keys are ignored, an empty set gives 0, a set whose
+ * sum is the point at infinity gives 0 whatever sigma is, a set that selects a key that did not decode
+ * gives 0 for exactly the items that name it, and an infinite sigma decodes and fails under a usable
+ * key sum.
+ *
+ * Host arrays: message j = msg_blob[msg_off[j] .. + msg_len[j]); bit i of valid_bitmap (ceil(n/8)
+ * bytes, LSB first, trailing bits 0).  Blocking.  CBFT_EINVAL before anything is launched, bitmap
+ * untouched: unknown key set, a null pointer that may not be null, set_of[i] >= s, msg_of[i] >= m,
+ * msg_len[j] > 0xFFFFFF00, set_of == nullptr with s != n, or msg_of == nullptr with m != n.  n = 0 is
+ * CBFT_OK.  Up to 2^26 items and CBFT_BLS_MULTISIG_MAX_SETS sets per call and device (CBFT_E2BIG: the
+ * per-set tables take up to 17.3 KB of device scratch each).  On a multi-GPU context each device
+ * verifies a contiguous slice of the items, summing only the sets and hashing only the messages that
+ * slice names. */
+#define CBFT_BLS_MULTISIG_MAX_SETS (1u << 16)
+int cbft_bls_verify_multisig_batch(cbft_ctx* ctx, uint32_t keyset, const uint8_t* signers256, size_t s,
+                                   const uint32_t* set_of, const uint8_t* sig33, const uint8_t* msg_blob,
+                                   const uint64_t* msg_off, const uint32_t* msg_len, size_t m, const uint32_t* msg_of,
+                                   size_t n, uint8_t* valid_bitmap);
+/* Device-resident form: bitmaps at d_signers256 (s x 256), message j at d_msg + j * msg_len, verdicts
+ * to d_valid (n bytes, 0 / 1), asynchronous on `stream` (nullptr = the context's own stream).  An
+ * out-of-range d_set_of or d_msg_of entry gives verdict 0.  Calls on different streams share the
+ * batch scratch and are ordered by the library.  Single-GPU contexts only. */
+int cbft_bls_verify_multisig_fixed_device(cbft_ctx* ctx, uint32_t keyset, const uint8_t* d_signers256, size_t s,
+                                          const uint32_t* d_set_of, const uint8_t* d_sig33, const uint8_t* d_msg,
+                                          uint32_t msg_len, size_t m, const uint32_t* d_msg_of, size_t n,
+                                          uint8_t* d_valid, void* stream);
+/* The s key sums alone: out65[j] (s x 65) and ok[j] (s bytes) are byte for byte what cbft_bls_sum_keys
+ * writes for bitmap j and what its key-status byte would be: the compressed sum and 1; 65 zero bytes
+ * and 0 when a selected key did not decode; 65 zero bytes and 0 for an empty set or a sum at infinity.
+ * Blocking.  s = 0 is CBFT_OK; more than CBFT_BLS_MULTISIG_MAX_SETS sets CBFT_E2BIG. */
+int cbft_bls_sum_keys_batch(cbft_ctx* ctx, uint32_t keyset, const uint8_t* signers256, size_t s, uint8_t* out65,
+                            uint8_t* ok);
+
 /* ------------------------------------------------------- ECDSA secp256k1 / SHA-256 ------------
  * Replaces concord::util::crypto::ECDSAVerifier (util/src/crypto_utils.cpp:34-64,231-236), i.e.
  * Crypto++ ECDSA<ECP, SHA256> on its default curve secp256k1.  Verdicts are those of OpenSSL 3.0.2
