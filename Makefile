@@ -12,8 +12,8 @@ ORACLE_LIB := oracle/libcbft_oracle.so
 # host SIMD emulation of the same source is exact).  Costs one v_mov_dpp per move.
 ROWFLAGS := -mllvm -amdgpu-dpp-combine=false
 
-.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim bls_combine_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test sanitize selftest
-all: lib oracle cpu host shim fe_row_shim bls_sign_shim bls_combine_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test selftest
+.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim bls_combine_shim bls_keygen_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test sanitize selftest
+all: lib oracle cpu host shim fe_row_shim bls_sign_shim bls_combine_shim bls_keygen_shim sha512_shim ecdsa_shim ecdsa_sign_shim host_util_test selftest
 
 lib: $(LIB)
 
@@ -62,7 +62,7 @@ $(CSRC)/cbft_rsa.o: $(CSRC)/cbft_rsa.cpp $(INTERNAL_DEPS)
 $(CSRC)/bls_sign_batch.o: $(CSRC)/bls_sign_batch.hip $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_bls_sign.o: $(CSRC)/cbft_bls_sign.cpp $(INTERNAL_DEPS) $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
+$(CSRC)/cbft_bls_sign.o: $(CSRC)/cbft_bls_sign.cpp $(INTERNAL_DEPS) $(CSRC)/bls_keygen_batch.h $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # BLS verification in batches over many messages: its own objects (the other BLS kernels are not touched)
@@ -88,6 +88,14 @@ $(CSRC)/bls_multisig_batch.o: $(CSRC)/bls_multisig_batch.hip $(BLS_MULTISIG_DEPS
 $(CSRC)/cbft_bls_multisig_batch.o: $(CSRC)/cbft_bls_multisig_batch.cpp $(INTERNAL_DEPS) $(BLS_MULTISIG_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# BLS key derivation and dealing in batches: its own objects (constant-time lane code; the other BLS kernels are not touched)
+BLS_KEYGEN_DEPS := $(CSRC)/bls_keygen_batch.h $(CSRC)/bls_sign_batch.h $(BLS_DEPS)
+$(CSRC)/bls_keygen_batch.o: $(CSRC)/bls_keygen_batch.hip $(BLS_KEYGEN_DEPS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/cbft_bls_keygen.o: $(CSRC)/cbft_bls_keygen.cpp $(INTERNAL_DEPS) $(BLS_KEYGEN_DEPS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 # ECDSA secp256k1 verification: its own objects (no other kernel is touched)
 ECDSA_DEPS := $(CSRC)/ecdsa_verify.h $(CSRC)/fe_secp256k1.h $(CSRC)/sc_secp256k1.h $(CSRC)/ge_secp256k1.h $(CSRC)/safegcd30.h $(CSRC)/sha256.h
 $(CSRC)/ecdsa_verify.o: $(CSRC)/ecdsa_verify.hip $(ECDSA_DEPS)
@@ -107,7 +115,7 @@ $(CSRC)/cbft_ecdsa_sign.o: $(CSRC)/cbft_ecdsa_sign.cpp $(INTERNAL_DEPS) $(ECDSA_
 $(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(INTERNAL_DEPS) $(CSRC)/bls_kernels.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/bls_combine_batch.o $(CSRC)/cbft_bls_combine_batch.o $(CSRC)/bls_multisig_batch.o $(CSRC)/cbft_bls_multisig_batch.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o $(CSRC)/ecdsa_sign.o $(CSRC)/cbft_ecdsa_sign.o
+$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/bls_combine_batch.o $(CSRC)/cbft_bls_combine_batch.o $(CSRC)/bls_multisig_batch.o $(CSRC)/cbft_bls_multisig_batch.o $(CSRC)/bls_keygen_batch.o $(CSRC)/cbft_bls_keygen.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o $(CSRC)/ecdsa_sign.o $(CSRC)/cbft_ecdsa_sign.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle: $(ORACLE_LIB)
@@ -144,7 +152,7 @@ HOST_SRC := $(HOST_DIR)/src/hip_ed25519.cpp $(HOST_DIR)/src/hip_rsa.cpp $(HOST_D
 MIRROR_SRC := $(wildcard $(HOST_DIR)/ref_mirror/src/*.cpp)
 HOST_INC := -Iinclude -I$(HOST_DIR)/include -I$(HOST_DIR)/ref_mirror/include -DCBFT_WITH_CLIENT_KEYS_MAP
 HOST_HDRS := $(wildcard $(HOST_DIR)/include/*.hpp $(HOST_DIR)/include/threshsign/*.hpp $(HOST_DIR)/ref_mirror/include/*.hpp $(HOST_DIR)/ref_mirror/include/threshsign/*.h)
-host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_bls_combine_host tests/cpp/test_bls_combine_plan_san tests/cpp/test_bls_multisig_host tests/cpp/test_bls_multisig_plan_san tests/cpp/test_ecdsa_host tests/cpp/test_ecdsa_sign_host tools/host_bench
+host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_bls_combine_host tests/cpp/test_bls_combine_plan_san tests/cpp/test_bls_multisig_host tests/cpp/test_bls_multisig_plan_san tests/cpp/test_bls_keygen_host tests/cpp/test_bls_keygen_san tests/cpp/test_ecdsa_host tests/cpp/test_ecdsa_sign_host tools/host_bench
 $(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB) $(ECDSA_SIGN_DEPS)
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN'
 tests/cpp/test_host: tests/cpp/test_host.cpp $(HOST_LIB)
@@ -176,6 +184,14 @@ tests/cpp/test_bls_multisig_host: tests/cpp/test_bls_multisig_host.cpp $(HOST_LI
 # the same test with the host sources compiled in under ASan + UBSan, for its --no-gpu mode (the planning of the
 # multisig verifyBatch; run by tests/test_cpp_bls_multisig_host.py as a stand-alone program, never loaded into python)
 tests/cpp/test_bls_multisig_plan_san: tests/cpp/test_bls_multisig_host.cpp $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB)
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $< $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+tests/cpp/test_bls_keygen_host: tests/cpp/test_bls_keygen_host.cpp $(HOST_LIB)
+	g++ -O2 -std=c++17 -Wall $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+# the same test with the host sources compiled in under ASan + UBSan, for its --no-gpu mode (sampling bounds, key
+# encodings, the crossover setting; run by tests/test_cpp_bls_keygen_host.py as a stand-alone program, never loaded into python)
+tests/cpp/test_bls_keygen_san: tests/cpp/test_bls_keygen_host.cpp $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB)
 	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $< $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_ecdsa_host: tests/cpp/test_ecdsa_host.cpp $(HOST_LIB)
@@ -213,6 +229,17 @@ $(BLS_COMBINE_SHIM): $(BLS_COMBINE_SHIM_DEPS)
 	g++ -O3 -funroll-loops -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $<
 $(BLS_COMBINE_SHIM_SAN): $(BLS_COMBINE_SHIM_DEPS)
 	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DBLS_COMBINE_SHIM_MAIN -I$(CSRC) -o $@ $<
+
+# host build of the batched BLS key derivation and dealing lane code (bls_keygen_batch.h) for tests/test_bls_keygen_cpu.py,
+# and the same source as a stand-alone program under ASan + UBSan (run by that test, never loaded into python)
+BLS_KEYGEN_SHIM := tests/cpp/libbls_keygen_shim.so
+BLS_KEYGEN_SHIM_SAN := tests/cpp/bls_keygen_shim_san
+BLS_KEYGEN_SHIM_DEPS := tests/cpp/bls_keygen_shim.cpp $(CSRC)/bls_keygen_batch.h $(CSRC)/bls_sign_batch.h $(CSRC)/bn254_*.h $(CSRC)/bls_ops.h $(CSRC)/sha256.h
+bls_keygen_shim: $(BLS_KEYGEN_SHIM) $(BLS_KEYGEN_SHIM_SAN)
+$(BLS_KEYGEN_SHIM): $(BLS_KEYGEN_SHIM_DEPS)
+	g++ -O3 -funroll-loops -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $< -lpthread
+$(BLS_KEYGEN_SHIM_SAN): $(BLS_KEYGEN_SHIM_DEPS)
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DBLS_KEYGEN_SHIM_MAIN -I$(CSRC) -o $@ $< -lpthread
 
 # host build of the row-parallel GF(2^255 - 19) code (fe25519_row.h) for tests/test_fe_row.py
 FE_ROW_SHIM := tests/cpp/libfe_row_shim.so
@@ -292,7 +319,8 @@ BLS_VERIFY_SELFTEST := tests/hip/libbls_verify_selftest.so
 BLS_COMBINE_SELFTEST := tests/hip/libbls_combine_selftest.so
 FE25519_SELFTEST := tests/hip/libfe25519_selftest.so
 ECDSA_SIGN_SELFTEST := tests/hip/libecdsa_sign_selftest.so
-selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST) $(BLS_COMBINE_SELFTEST) $(FE25519_SELFTEST) $(ECDSA_SIGN_SELFTEST)
+BLS_KEYGEN_SELFTEST := tests/hip/libbls_keygen_selftest.so
+selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST) $(BLS_COMBINE_SELFTEST) $(FE25519_SELFTEST) $(ECDSA_SIGN_SELFTEST) $(BLS_KEYGEN_SELFTEST)
 # test-only device harness of the ECDSA signing lane code, one function per launch (tests/test_ecdsa_sign_gpu.py)
 $(ECDSA_SIGN_SELFTEST): tests/hip/ecdsa_sign_selftest.hip $(CSRC)/ecdsa_sign.hip $(ECDSA_SIGN_DEPS)
 	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
@@ -319,4 +347,8 @@ $(BLS_VERIFY_SELFTEST): tests/hip/bls_verify_selftest.hip $(CSRC)/bls_verify_bat
 # test-only device harness of the batched BLS combination: the product kernels timed stage by stage, beside
 # the constant-time signing kernel on the same points (tools/bls_combine_bench.py)
 $(BLS_COMBINE_SELFTEST): tests/hip/bls_combine_selftest.hip $(CSRC)/bls_combine_batch.hip $(BLS_COMBINE_DEPS) $(LIB)
+	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -shared -o $@ $< -Lconcord-bft_amd -lcbft_hipcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+# test-only device harness of the batched BLS key derivation: the product kernel beside the rejected geometry (the
+# row-parallel comb over a grid), each timed (tools/bls_keygen_bench.py)
+$(BLS_KEYGEN_SELFTEST): tests/hip/bls_keygen_selftest.hip $(CSRC)/bls_keygen_batch.hip $(BLS_KEYGEN_DEPS) $(LIB)
 	$(HIPCC) $(HIPFLAGS) $(ROWFLAGS) -shared -o $@ $< -Lconcord-bft_amd -lcbft_hipcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'

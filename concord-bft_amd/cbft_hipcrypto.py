@@ -157,6 +157,13 @@ ABI = [
       ctypes.c_void_p]),
     ("cbft_bls_sum_keys_batch", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_bls_public_key_batch", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_bls_public_key_fixed_device", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    ("cbft_bls_keygen_threshold", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
+      ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_bls_combine_partial", ctypes.c_int,
      [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int,
       ctypes.c_void_p]),
@@ -896,6 +903,43 @@ class Context:
         out = ctypes.create_string_buffer(65)
         _check(self.lib.cbft_bls_public_key(self.handle, sk.to_bytes(32, "big"), out), "cbft_bls_public_key")
         return out.raw
+
+    def bls_public_key_batch(self, sks: Sequence[int]):
+        """(keys, ok): keys[i] = (sks[i] mod r) * g2, 65 compressed bytes, what bls_public_key gives for that
+        scalar, and ok[i] = 1; a scalar that is 0 mod r gives 65 zero bytes and ok[i] = 0.  Scalars are
+        integers below 2^256."""
+        n = len(sks)
+        sk = np.frombuffer(b"".join(int(x).to_bytes(32, "big") for x in sks), dtype=np.uint8) if n else np.zeros(
+            1, dtype=np.uint8)
+        out = np.zeros((max(1, n), 65), dtype=np.uint8)
+        ok = np.zeros(max(1, n), dtype=np.uint8)
+        _check(self.lib.cbft_bls_public_key_batch(self.handle, _ptr(sk), n, _ptr(out), _ptr(ok)),
+               "cbft_bls_public_key_batch")
+        return [out[i].tobytes() for i in range(n)], ok[:n]
+
+    def bls_public_key_fixed_device(self, d_sk32: int, n: int, d_out65: int, d_ok: int, stream: int = 0):
+        """n scalars (32 bytes big-endian each) at d_sk32 -> keys at d_out65, status bytes at d_ok; raw device
+        addresses, asynchronous on `stream`."""
+        _check(self.lib.cbft_bls_public_key_fixed_device(
+            self.handle, ctypes.c_void_p(d_sk32), n, ctypes.c_void_p(d_out65), ctypes.c_void_p(d_ok),
+            ctypes.c_void_p(stream)), "cbft_bls_public_key_fixed_device")
+
+    def bls_keygen_threshold(self, coeffs: Sequence[int], n: int):
+        """Shamir dealing of f(x) = sum coeffs[j] x^j over n shares: (sks, vks, pk, ok) with sks[i - 1] = f(i) mod r
+        (integers), vks[i - 1] = f(i) * g2, pk = coeffs[0] * g2 (65 bytes each) and ok the n + 1 status bytes
+        (ok[0] for pk, ok[i] for share i)."""
+        k = len(coeffs)
+        co = np.frombuffer(b"".join(int(x).to_bytes(32, "big") for x in coeffs), dtype=np.uint8) if k else np.zeros(
+            1, dtype=np.uint8)
+        m = max(1, n)
+        sk = np.zeros((m, 32), dtype=np.uint8)
+        vk = np.zeros((m, 65), dtype=np.uint8)
+        pk = np.zeros(65, dtype=np.uint8)
+        ok = np.zeros(m + 1, dtype=np.uint8)
+        _check(self.lib.cbft_bls_keygen_threshold(self.handle, _ptr(co), k, n, _ptr(sk), _ptr(vk), _ptr(pk), _ptr(ok)),
+               "cbft_bls_keygen_threshold")
+        return ([int.from_bytes(sk[i].tobytes(), "big") for i in range(n)], [vk[i].tobytes() for i in range(n)],
+                pk.tobytes(), ok[:n + 1])
 
     def set_profiling(self, on: bool = True, per_batch: bool = False):
         mode = (2 if per_batch else 1) if on else 0

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "bls_kernels.h"
+#include "bls_keygen_batch.h"
 #include "bls_sign_batch.h"
 #include "cbft_internal.h"
 
@@ -88,7 +89,12 @@ int cbft_bls_load_signers(cbft_ctx* c, const uint8_t* sk32, const uint32_t* ids,
   if (e == hipSuccess)
     e = cbft_bls_sign_launch_keys(ds.as<uint32_t>(), ds.as<uint32_t>() + 8 * (size_t)nkeys, nkeys, st.rec.as<uint32_t>(),
                                   c->stream);
-  for (uint32_t i = 0; i < nkeys && e == hipSuccess; i++)  // vk_i = sk_i * g2
+  // vk_i = sk_i * g2: one key per lane from the measured crossover on (bls_keygen_batch.h), else a launch per key
+  const bool batch = nkeys >= CBFT_BLS_KEYGEN_BATCH_MIN_DEFAULT;
+  if (e == hipSuccess && batch)
+    e = cbft_bls_keygen_launch(c->bls_pub_tbl.as<uint32_t>(), nullptr, ds.as<uint32_t>(), nkeys, st.vk65.as<uint8_t>(),
+                               nullptr, c->stream);
+  for (uint32_t i = 0; i < nkeys && !batch && e == hipSuccess; i++)
     e = cbft_bls_launch_pubkey_row(c->bls_pub_tbl.as<uint32_t>(), ds.as<uint32_t>() + 8 * (size_t)i,
                                    st.vk65.as<uint8_t>() + CBFT_BLS_G2_BYTES * (size_t)i, c->stream);
   if (ds.p) {  // the scalars leave the device, whatever happened

@@ -360,6 +360,7 @@ void cbft_close(cbft_ctx* c) {
   cbft_bls_verify_batch_release(c);
   cbft_bls_combine_batch_release(c);
   cbft_bls_multisig_batch_release(c);
+  cbft_bls_keygen_release(c);
   cbft_ecdsa_release(c);
   cbft_ecdsa_sign_release(c);
   for (auto& kv : c->rsa_tables) kv.second.rec.release();

@@ -389,6 +389,12 @@ struct cbft_ctx {
     ScratchGuard scratch;  // the verification's scratch, then per set: lines, affine sum, partials, flag (public)
     DevBuf in, sets, out;  // packed inputs, signer bitmaps / verdict bytes (or key sums) of a host-array batch
   } blsm;
+  // BLS key derivation and dealing in batches (cbft_bls_keygen.cpp)
+  struct {
+    ScratchGuard scratch;  // a dealing's coefficients, their Montgomery forms and shares: secret, zeroed by every call
+    HostBuf hin;           // pinned staging of scalars / coefficients, wiped by every call
+    DevBuf in, out;        // scalars (zeroed by every call) / keys | ok bytes of a host-array batch
+  } blsk;
   // ECDSA secp256k1 verification (cbft_ecdsa.cpp)
   std::unordered_map<uint32_t, EcdsaKeyTable> ecdsa_tables;
   uint32_t next_ecdsa_id = 1;
@@ -423,6 +429,7 @@ void cbft_bls_sign_release(cbft_ctx* c);
 void cbft_bls_verify_batch_release(cbft_ctx* c);
 void cbft_bls_combine_batch_release(cbft_ctx* c);
 void cbft_bls_multisig_batch_release(cbft_ctx* c);
+void cbft_bls_keygen_release(cbft_ctx* c);
 void cbft_ecdsa_release(cbft_ctx* c);
 void cbft_ecdsa_sign_release(cbft_ctx* c);
 // 32-byte big-endian BLS scalar -> 8 little-endian words reduced mod r, as cbft_bls_sign takes it;

@@ -9,6 +9,9 @@
 //                          BlsThresholdAccumulator.cpp:29-55, BlsMultisigAccumulator.cpp:30-65,
 //                          BlsAlmostMultisigAccumulator.cpp:28-46
 //   BlsThresholdSigner     threshsign/src/bls/relic/BlsThresholdSigner.cpp:25-47
+//   BlsThresholdKeygen, BlsMultisigKeygen, BlsThresholdFactory
+//                          BlsThresholdKeygen.cpp:28-50, BlsMultisigKeygen.cpp:22-40,
+//                          BlsThresholdFactory.cpp:41-119 (what Cryptosystem::createThresholdFactory returns)
 //
 // Difference by design: where the reference verifies pending shares one pairing pair at a time
 // (ThresholdAccumulatorBase::verifyPendingShares), this accumulator verifies all pending shares
@@ -25,9 +28,12 @@
 #include <memory>
 #include <mutex>
 #include <string>
+#include <tuple>
+#include <utility>
 #include <vector>
 
 #include "threshsign/IThresholdAccumulator.h"
+#include "threshsign/IThresholdFactory.h"
 #include "threshsign/IThresholdSigner.h"
 #include "threshsign/IThresholdVerifier.h"
 #include "threshsign/VectorOfShares.h"
@@ -52,7 +58,10 @@ class BlsPublicKey : public IShareVerificationKey {
 
 class BlsSecretKey : public IShareSecretKey {
  public:
+  BlsSecretKey() = default;                           // the number 0, toString() empty
   explicit BlsSecretKey(const std::string& decimal);  // throws std::invalid_argument
+  explicit BlsSecretKey(const std::array<uint8_t, 32>& bigEndian);  // toString() is its decimal form
+  ~BlsSecretKey() override;                           // wipes both copies
   std::string toString() const override { return dec_; }
   const std::array<uint8_t, 32>& bytes() const { return be_; }  // big-endian
 
@@ -301,6 +310,91 @@ class BlsThresholdSigner : public IThresholdSigner {
   std::shared_ptr<BlsEngine> engine_;
   std::mutex table_mu_;        // guards the registration below (concurrent first batches)
   uint32_t signer_table_ = 0;  // one-key table of the engine's context, loaded by the first GPU batch
+};
+
+// ------------------------------------------------------------------------------ key generation
+// Smallest number of keys (shares plus the group key) that a keygen derives with ONE batch call
+// (cbft_bls_keygen_threshold, cbft_bls_public_key_batch; $CBFT_BLS_KEYGEN_BATCH_MIN overrides, default
+// CBFT_BLS_KEYGEN_BATCH_MIN_DEFAULT of cbft_hipcrypto.h); fewer loop the lone cbft_bls_public_key, with the
+// shares dealt on the host.  The keys are the same.  The measured crossover.
+size_t keygenBatchMin();
+// 32 big-endian bytes uniform in [1, r): OpenSSL RAND_bytes masked to 254 bits, drawn again while the
+// value is 0 or >= r.  Throws std::runtime_error if the generator fails.
+void sampleScalar(std::array<uint8_t, 32>& out);
+bool scalarInRange(const std::array<uint8_t, 32>& bigEndian);  // 1 <= value < r
+
+// The reference keygens' accessors (IThresholdKeygen<SK, PK>): group secret and PK, share secret keys and
+// share verification keys indexed from 1 (entry 0 of the vectors is unused).
+class BlsThresholdKeygenBase {
+ public:
+  virtual ~BlsThresholdKeygenBase() = default;
+  NumSharesType getNumSigners() const { return num_; }
+  const BlsSecretKey& getSecretKey() const { return sk_; }
+  const BlsPublicKey& getPublicKey() const { return pk_; }
+  const BlsSecretKey& getShareSecretKey(ShareID i) const { return skShares_.at((size_t)i); }
+  const BlsPublicKey& getShareVerificationKey(ShareID i) const { return pkShares_.at((size_t)i); }
+  const std::vector<BlsSecretKey>& getShareSecretKeys() const { return skShares_; }
+  const std::vector<BlsPublicKey>& getShareVerificationKeys() const { return pkShares_; }
+
+ protected:
+  explicit BlsThresholdKeygenBase(NumSharesType numSigners);
+  // scalars[0] = the group secret, scalars[i] = share i -> sk_, skShares_, pk_, pkShares_ (one batch call
+  // from keygenBatchMin() keys on, else lone calls); throws std::runtime_error if a scalar is 0 mod r
+  void deriveKeys(std::vector<std::array<uint8_t, 32>>& scalars);
+  void setKeys(const std::vector<std::array<uint8_t, 32>>& scalars, const uint8_t* keys65, const uint8_t* ok);
+
+  NumSharesType num_;
+  BlsSecretKey sk_;
+  BlsPublicKey pk_;
+  std::vector<BlsSecretKey> skShares_;
+  std::vector<BlsPublicKey> pkShares_;
+  std::shared_ptr<BlsEngine> engine_;
+};
+
+// Shamir dealing: sk_i = f(i) for a polynomial of degree reqSigners - 1 over Fr, vk_i = sk_i * g2,
+// PK = f(0) * g2.  1 <= reqSigners <= numSigners <= 2048 (std::invalid_argument).
+class BlsThresholdKeygen : public BlsThresholdKeygenBase {
+ public:
+  BlsThresholdKeygen(NumSharesType reqSigners, NumSharesType numSigners);  // coefficients from sampleScalar
+  // the reqSigners coefficients c_0 .. c_{k-1} given (32 bytes big-endian each, reduced mod r): for tests
+  BlsThresholdKeygen(NumSharesType reqSigners, NumSharesType numSigners,
+                     const std::vector<std::array<uint8_t, 32>>& coefficients);
+
+ private:
+  void deal(NumSharesType reqSigners, std::vector<std::array<uint8_t, 32>>& coefficients);
+};
+
+// numSigners independent secrets, group secret = their sum mod r, PK = that sum * g2 (= the sum of the vk_i).
+class BlsMultisigKeygen : public BlsThresholdKeygenBase {
+ public:
+  explicit BlsMultisigKeygen(NumSharesType numSigners);  // secrets from sampleScalar
+  BlsMultisigKeygen(NumSharesType numSigners, const std::vector<std::array<uint8_t, 32>>& secrets);  // for tests
+
+ private:
+  void sum(std::vector<std::array<uint8_t, 32>>& secrets);
+};
+
+// The reference's BlsThresholdFactory without its curve parameter (BN-P254 is the only curve).  As
+// Cryptosystem does (forceMultisig_, ThresholdSignaturesTypes.cpp:31), reqSigners == numSigners takes the
+// multisig scheme whatever the flag says.
+class BlsThresholdFactory : public IThresholdFactory {
+ public:
+  explicit BlsThresholdFactory(bool useMultisig = false) : useMultisig_(useMultisig) {}
+  std::unique_ptr<BlsThresholdKeygenBase> newKeygen(NumSharesType reqSigners, NumSharesType numSigners) const;
+  // publicKeyStr: 130 hex characters (ignored by the multisig scheme); verifKeysStr[1 .. numSigners] likewise
+  IThresholdVerifier* newVerifier(ShareID reqSigners, ShareID numSigners, const char* publicKeyStr,
+                                  const std::vector<std::string>& verifKeysStr) const override;
+  IThresholdSigner* newSigner(ShareID id, const char* secretKeyStr) const override;  // decimal secret key
+  std::tuple<std::vector<IThresholdSigner*>, IThresholdVerifier*> newRandomSigners(
+      NumSharesType reqSigners, NumSharesType numSigners) const override;
+  // multisig only, as the reference's (std::runtime_error otherwise)
+  std::pair<std::unique_ptr<IShareSecretKey>, std::unique_ptr<IShareVerificationKey>> newKeyPair() const override;
+  bool multisigFor(NumSharesType reqSigners, NumSharesType numSigners) const {
+    return useMultisig_ || reqSigners == numSigners;
+  }
+
+ private:
+  bool useMultisig_;
 };
 
 }  // namespace Hip

@@ -7,6 +7,10 @@
 #include <stdexcept>
 #include <unordered_map>
 
+#include <openssl/bn.h>
+#include <openssl/crypto.h>
+#include <openssl/rand.h>
+
 #include "cbft_hipcrypto.h"
 
 namespace BLS {
@@ -83,6 +87,31 @@ BlsSecretKey::BlsSecretKey(const std::string& decimal) : dec_(decimal) {
     }
     if (carry) throw std::invalid_argument("BLS secret key: exceeds 256 bits");
   }
+}
+
+BlsSecretKey::BlsSecretKey(const std::array<uint8_t, 32>& bigEndian) : be_(bigEndian) {
+  // decimal digits by repeated division by 10 (most significant byte first)
+  std::array<uint8_t, 32> t = bigEndian;
+  std::string rev;
+  for (;;) {
+    unsigned rem = 0, any = 0;
+    for (size_t i = 0; i < 32; i++) {
+      const unsigned v = rem * 256u + t[i];
+      t[i] = (uint8_t)(v / 10u);
+      rem = v % 10u;
+      any |= t[i];
+    }
+    rev.push_back((char)('0' + rem));
+    if (!any) break;
+  }
+  dec_.assign(rev.rbegin(), rev.rend());
+  OPENSSL_cleanse(&rev[0], rev.size());
+  OPENSSL_cleanse(t.data(), t.size());
+}
+
+BlsSecretKey::~BlsSecretKey() {
+  if (!dec_.empty()) OPENSSL_cleanse(&dec_[0], dec_.size());
+  OPENSSL_cleanse(be_.data(), be_.size());
 }
 
 // ------------------------------------------------------------------------------ verifiers
@@ -631,6 +660,277 @@ void BlsThresholdSigner::signBatch(const std::vector<BlsSignRequest>& requests) 
   check(cbft_bls_sign_batch(engine_->ctx(), signer_table_, nullptr, blob.data(), off.data(), len.data(), n, out.data()),
         "cbft_bls_sign_batch");
   for (size_t i = 0; i < n; i++) std::memcpy(requests[i].out, out.data() + 37 * i, 37);
+}
+
+// ------------------------------------------------------------------------------ key generation
+using Scalar = std::array<uint8_t, 32>;
+
+// r, the order of G1 / G2, big-endian
+static const Scalar kGroupOrder = {0x25, 0x23, 0x64, 0x82, 0x40, 0x00, 0x00, 0x01, 0xba, 0x34, 0x4d,
+                                   0x80, 0x00, 0x00, 0x00, 0x07, 0xff, 0x9f, 0x80, 0x00, 0x00, 0x00,
+                                   0x00, 0x10, 0xa1, 0x00, 0x00, 0x00, 0x00, 0x00, 0x00, 0x0d};
+
+size_t keygenBatchMin() {  // read at every call: a keygen is rare, and tests switch it
+  const char* e = std::getenv("CBFT_BLS_KEYGEN_BATCH_MIN");
+  const long long x = e ? std::atoll(e) : 0;
+  return x > 0 ? (size_t)x : (size_t)CBFT_BLS_KEYGEN_BATCH_MIN_DEFAULT;
+}
+
+bool scalarInRange(const Scalar& be) {
+  unsigned any = 0;
+  int lt = 0;  // the first differing byte decides; no early exit on a secret
+  for (size_t i = 0; i < 32; i++) {
+    any |= be[i];
+    const int d = (int)be[i] - (int)kGroupOrder[i];
+    lt = lt ? lt : d;
+  }
+  return any != 0 && lt < 0;
+}
+
+void sampleScalar(Scalar& out) {
+  for (;;) {
+    if (RAND_bytes(out.data(), 32) != 1) throw std::runtime_error("BLS keygen: RAND_bytes failed");
+    out[0] &= 0x3f;  // r has 254 bits: more than half of the draws are kept
+    if (scalarInRange(out)) return;
+  }
+}
+
+static void wipeScalars(std::vector<Scalar>& v) {
+  if (!v.empty()) OPENSSL_cleanse(v.data(), v.size() * sizeof(Scalar));
+}
+
+BlsThresholdKeygenBase::BlsThresholdKeygenBase(NumSharesType numSigners) : num_(numSigners) {
+  if (numSigners < 1 || numSigners > MAX_NUM_OF_SHARES)
+    throw std::invalid_argument("BLS keygen: need 1 <= numSigners <= 2048");
+  skShares_.resize((size_t)numSigners + 1);
+  pkShares_.resize((size_t)numSigners + 1);
+  engine_ = BlsEngine::get();
+}
+
+void BlsThresholdKeygenBase::setKeys(const std::vector<Scalar>& scalars, const uint8_t* keys65, const uint8_t* ok) {
+  for (size_t i = 0; i < scalars.size(); i++)
+    if (!ok[i]) throw std::runtime_error("BLS keygen: a key's scalar is 0 mod r");
+  sk_ = BlsSecretKey(scalars[0]);
+  pk_ = BlsPublicKey(toHex(keys65, 65));
+  for (size_t i = 1; i < scalars.size(); i++) {
+    skShares_[i] = BlsSecretKey(scalars[i]);
+    pkShares_[i] = BlsPublicKey(toHex(keys65 + 65 * i, 65));
+  }
+}
+
+void BlsThresholdKeygenBase::deriveKeys(std::vector<Scalar>& scalars) {
+  const size_t m = scalars.size();
+  std::vector<uint8_t> keys(65 * m), ok(m, 0);
+  if (m >= keygenBatchMin()) {
+    check(cbft_bls_public_key_batch(engine_->ctx(), scalars[0].data(), m, keys.data(), ok.data()),
+          "cbft_bls_public_key_batch");
+  } else {
+    for (size_t i = 0; i < m; i++) {
+      const int rc = cbft_bls_public_key(engine_->ctx(), scalars[i].data(), &keys[65 * i]);
+      if (rc != CBFT_EINVAL) check(rc, "cbft_bls_public_key");  // CBFT_EINVAL: the scalar is 0 mod r
+      ok[i] = rc == CBFT_OK;
+    }
+  }
+  setKeys(scalars, keys.data(), ok.data());
+}
+
+BlsThresholdKeygen::BlsThresholdKeygen(NumSharesType reqSigners, NumSharesType numSigners)
+    : BlsThresholdKeygenBase(numSigners) {
+  if (reqSigners < 1 || reqSigners > numSigners)
+    throw std::invalid_argument("BLS keygen: need 1 <= reqSigners <= numSigners");
+  std::vector<Scalar> c((size_t)reqSigners);
+  for (auto& x : c) sampleScalar(x);
+  try {
+    deal(reqSigners, c);
+  } catch (...) {
+    wipeScalars(c);
+    throw;
+  }
+  wipeScalars(c);
+}
+
+BlsThresholdKeygen::BlsThresholdKeygen(NumSharesType reqSigners, NumSharesType numSigners,
+                                       const std::vector<Scalar>& coefficients)
+    : BlsThresholdKeygenBase(numSigners) {
+  if (reqSigners < 1 || reqSigners > numSigners || coefficients.size() != (size_t)reqSigners)
+    throw std::invalid_argument("BLS keygen: need 1 <= reqSigners <= numSigners and reqSigners coefficients");
+  std::vector<Scalar> c(coefficients);
+  try {
+    deal(reqSigners, c);
+  } catch (...) {
+    wipeScalars(c);
+    throw;
+  }
+  wipeScalars(c);
+}
+
+// f(i) mod r for i = 1 .. n on the host (below the crossover): Horner with OpenSSL's constant-time flag set
+static void dealOnHost(const std::vector<Scalar>& c, std::vector<Scalar>& scalars) {
+  BN_CTX* bctx = BN_CTX_new();
+  BIGNUM* r = BN_bin2bn(kGroupOrder.data(), 32, nullptr);
+  BIGNUM* acc = BN_new();
+  BIGNUM* x = BN_new();
+  BIGNUM* cj = BN_new();
+  bool good = bctx && r && acc && x && cj;
+  if (good) {
+    BN_set_flags(acc, BN_FLG_CONSTTIME);
+    BN_set_flags(cj, BN_FLG_CONSTTIME);
+  }
+  for (size_t i = 0; good && i < scalars.size(); i++) {  // i = 0: f(0) = c_0 mod r
+    good = BN_set_word(x, (BN_ULONG)i) == 1;
+    BN_zero(acc);
+    for (size_t j = c.size(); good && j-- > 0;) {
+      good = BN_bin2bn(c[j].data(), 32, cj) != nullptr && BN_mod_mul(acc, acc, x, r, bctx) == 1 &&
+             BN_mod_add(acc, acc, cj, r, bctx) == 1;
+    }
+    good = good && BN_bn2binpad(acc, scalars[i].data(), 32) == 32;
+  }
+  BN_clear_free(acc);
+  BN_clear_free(cj);
+  BN_free(x);
+  BN_free(r);
+  BN_CTX_free(bctx);
+  if (!good) throw std::runtime_error("BLS keygen: host dealing failed");
+}
+
+void BlsThresholdKeygen::deal(NumSharesType reqSigners, std::vector<Scalar>& c) {
+  const size_t n = (size_t)num_, m = n + 1;
+  std::vector<Scalar> scalars(m);
+  try {
+    if (m >= keygenBatchMin()) {
+      std::vector<uint8_t> keys(65 * m), ok(m, 0);
+      const int rc = cbft_bls_keygen_threshold(engine_->ctx(), c[0].data(), (uint32_t)reqSigners, (uint32_t)n,
+                                               scalars[1].data(), &keys[65], keys.data(), ok.data());
+      check(rc, "cbft_bls_keygen_threshold");
+      {  // the group secret is c_0 mod r = f(0)
+        std::vector<Scalar> c0(1, c[0]), s0(1);
+        dealOnHost(c0, s0);
+        scalars[0] = s0[0];
+        wipeScalars(c0);
+        wipeScalars(s0);
+      }
+      setKeys(scalars, keys.data(), ok.data());
+    } else {
+      dealOnHost(c, scalars);
+      deriveKeys(scalars);
+    }
+  } catch (...) {
+    wipeScalars(scalars);
+    throw;
+  }
+  wipeScalars(scalars);
+}
+
+BlsMultisigKeygen::BlsMultisigKeygen(NumSharesType numSigners) : BlsThresholdKeygenBase(numSigners) {
+  std::vector<Scalar> s((size_t)numSigners);
+  for (auto& x : s) sampleScalar(x);
+  try {
+    sum(s);
+  } catch (...) {
+    wipeScalars(s);
+    throw;
+  }
+  wipeScalars(s);
+}
+
+BlsMultisigKeygen::BlsMultisigKeygen(NumSharesType numSigners, const std::vector<Scalar>& secrets)
+    : BlsThresholdKeygenBase(numSigners) {
+  if (secrets.size() != (size_t)numSigners) throw std::invalid_argument("BLS keygen: need numSigners secrets");
+  for (const auto& x : secrets)
+    if (!scalarInRange(x)) throw std::invalid_argument("BLS keygen: a secret outside [1, r)");
+  std::vector<Scalar> s(secrets);
+  try {
+    sum(s);
+  } catch (...) {
+    wipeScalars(s);
+    throw;
+  }
+  wipeScalars(s);
+}
+
+// acc = (acc + x) mod r for acc, x < r, big-endian bytes; the subtraction of r by a mask
+static void addModOrder(Scalar& acc, const Scalar& x) {
+  unsigned carry = 0;
+  for (int i = 31; i >= 0; i--) {
+    const unsigned v = (unsigned)acc[(size_t)i] + x[(size_t)i] + carry;
+    acc[(size_t)i] = (uint8_t)v;
+    carry = v >> 8;
+  }  // r < 2^254: no carry out
+  Scalar t;
+  int borrow = 0;
+  for (int i = 31; i >= 0; i--) {
+    const int v = (int)acc[(size_t)i] - (int)kGroupOrder[(size_t)i] - borrow;
+    t[(size_t)i] = (uint8_t)v;
+    borrow = v < 0;
+  }
+  const uint8_t keep = (uint8_t)(0 - (unsigned)(1 - borrow));  // no borrow: acc >= r, the difference stands
+  for (size_t i = 0; i < 32; i++) acc[i] = (uint8_t)((t[i] & keep) | (acc[i] & (uint8_t)~keep));
+  OPENSSL_cleanse(t.data(), t.size());
+}
+
+void BlsMultisigKeygen::sum(std::vector<Scalar>& secrets) {
+  std::vector<Scalar> scalars((size_t)num_ + 1);
+  scalars[0].fill(0);
+  for (size_t i = 0; i < secrets.size(); i++) {
+    scalars[i + 1] = secrets[i];
+    addModOrder(scalars[0], secrets[i]);
+  }
+  try {
+    deriveKeys(scalars);
+  } catch (...) {
+    wipeScalars(scalars);
+    throw;
+  }
+  wipeScalars(scalars);
+}
+
+// ------------------------------------------------------------------------------ factory
+std::unique_ptr<BlsThresholdKeygenBase> BlsThresholdFactory::newKeygen(NumSharesType reqSigners,
+                                                                       NumSharesType numSigners) const {
+  if (multisigFor(reqSigners, numSigners)) return std::unique_ptr<BlsThresholdKeygenBase>(new BlsMultisigKeygen(numSigners));
+  return std::unique_ptr<BlsThresholdKeygenBase>(new BlsThresholdKeygen(reqSigners, numSigners));
+}
+
+IThresholdVerifier* BlsThresholdFactory::newVerifier(ShareID reqSigners, ShareID numSigners, const char* publicKeyStr,
+                                                     const std::vector<std::string>& verifKeysStr) const {
+  if (numSigners < 1 || verifKeysStr.size() != (size_t)numSigners + 1)
+    throw std::invalid_argument("BLS factory: need numSigners + 1 verification key strings (entry 0 unused)");
+  const std::vector<std::string> vks(verifKeysStr.begin() + 1, verifKeysStr.end());
+  if (multisigFor(reqSigners, numSigners)) return new BlsMultisigVerifier(reqSigners, numSigners, vks);
+  return new BlsThresholdVerifier(publicKeyStr ? std::string(publicKeyStr) : std::string(), reqSigners, numSigners, vks);
+}
+
+IThresholdSigner* BlsThresholdFactory::newSigner(ShareID id, const char* secretKeyStr) const {
+  if (!secretKeyStr) throw std::invalid_argument("BLS factory: no secret key");
+  return new BlsThresholdSigner(id, secretKeyStr);
+}
+
+std::tuple<std::vector<IThresholdSigner*>, IThresholdVerifier*> BlsThresholdFactory::newRandomSigners(
+    NumSharesType reqSigners, NumSharesType numSigners) const {
+  std::unique_ptr<BlsThresholdKeygenBase> keygen(newKeygen(reqSigners, numSigners));
+  std::vector<IThresholdSigner*> signers((size_t)numSigners + 1, nullptr);  // indexed from 1
+  std::vector<std::string> vks((size_t)numSigners + 1);
+  IThresholdVerifier* verifier = nullptr;
+  try {
+    for (ShareID i = 1; i <= numSigners; i++) {
+      vks[(size_t)i] = keygen->getShareVerificationKey(i).toString();
+      // the key the keygen derived is handed over: no second sk * g2 per signer
+      signers[(size_t)i] = new BlsThresholdSigner(i, keygen->getShareSecretKey(i).toString(), vks[(size_t)i]);
+    }
+    const std::string pk = keygen->getPublicKey().toString();
+    verifier = newVerifier(reqSigners, numSigners, pk.c_str(), vks);
+  } catch (...) {
+    for (auto* s : signers) delete s;
+    throw;
+  }
+  return std::make_tuple(signers, verifier);
+}
+
+std::pair<std::unique_ptr<IShareSecretKey>, std::unique_ptr<IShareVerificationKey>> BlsThresholdFactory::newKeyPair() const {
+  if (!useMultisig_) throw std::runtime_error("BlsThresholdFactory::newKeyPair allowed for multisig only");
+  BlsMultisigKeygen keygen(1);
+  return std::make_pair(std::unique_ptr<IShareSecretKey>(new BlsSecretKey(keygen.getShareSecretKey(1))),
+                        std::unique_ptr<IShareVerificationKey>(new BlsPublicKey(keygen.getShareVerificationKey(1))));
 }
 
 }  // namespace Hip

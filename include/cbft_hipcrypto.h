@@ -96,6 +96,9 @@ void cbft_close(cbft_ctx* ctx);
  *   CBFT_BLS_SIGN_BATCH_MIN smallest BlsThresholdSigner::signBatch that signs in one batch call
  *                         instead of a loop of cbft_bls_sign (host layer; default
  *                         CBFT_BLS_SIGN_BATCH_MIN_DEFAULT in threshsign/bls_hip.hpp)
+ *   CBFT_BLS_KEYGEN_BATCH_MIN fewest keys a BLS::Hip keygen derives with one batch call instead of a
+ *                         loop of the lone call (host layer; default CBFT_BLS_KEYGEN_BATCH_MIN_DEFAULT
+ *                         below; the C library itself reads no environment)
  * Geometry and scheduling switches that tests exercise on purpose (both ladder layouts, other B
  * comb radices, the three-kernel path at small sizes, ...) are per-context options, set after
  * cbft_open and before the first batch that should use them; a multi-GPU context applies them
@@ -427,6 +430,37 @@ int cbft_bls_verify_multisig_partials(cbft_ctx* ctx, const uint8_t* msg, uint32_
 /* The signer's public (share verification) key: out65 = sk * g2 compressed, sk = 32 bytes
  * big-endian (< r) (BlsThresholdSigner's publicKey_, IThresholdSigner::getShareVerificationKey). */
 int cbft_bls_public_key(cbft_ctx* ctx, const uint8_t* sk32, uint8_t* out65);
+
+/* ---- Batched key derivation and threshold key generation: the batch form of cbft_bls_public_key, one
+ * key per GPU lane, constant time in the scalar (csrc/bls_keygen_batch.h), and BlsThresholdKeygen's
+ * Shamir dealing on top of it.  Scalars and coefficients are 32 bytes big-endian, any value, reduced
+ * mod r.  Secrets cross in pinned staging that is wiped, and every device copy is cleared before the
+ * call returns.  On a multi-GPU context all three run on the lowest device. */
+#define CBFT_BLS_KEYGEN_MAX_BATCH ((size_t)1 << 20)   /* CBFT_E2BIG above */
+/* The smallest signer table whose verification keys cbft_bls_load_signers derives with one batch launch
+ * instead of one launch per key, and the smallest key set a caller should hand to the batch call
+ * instead of looping the lone one (the measured crossover). */
+#define CBFT_BLS_KEYGEN_BATCH_MIN_DEFAULT 6
+
+/* out65[i] = (sk_i mod r) * g2 compressed, byte for byte what cbft_bls_public_key gives for that
+ * scalar; ok[i] = 1.  A scalar that is 0 mod r: 65 zero bytes, ok[i] = 0, neighbours unaffected.
+ * Host arrays, blocking.  n = 0 is CBFT_OK.  Null pointer: CBFT_EINVAL, outputs untouched. */
+int cbft_bls_public_key_batch(cbft_ctx* ctx, const uint8_t* sk32 /* n x 32 */, size_t n,
+                              uint8_t* out65 /* n x 65 */, uint8_t* ok /* n */);
+/* Device-resident, asynchronous on `stream` (nullptr: the context's own).  The kernel keeps no scratch:
+ * calls on different streams share only the public comb of g2.  The caller owns and clears d_sk32.
+ * Single-GPU contexts only. */
+int cbft_bls_public_key_fixed_device(cbft_ctx* ctx, const uint8_t* d_sk32, size_t n, uint8_t* d_out65,
+                                     uint8_t* d_ok, void* stream);
+
+/* Shamir dealing (BlsThresholdKeygen): coeff32 = k coefficients c_0..c_{k-1} (32 bytes big-endian,
+ * reduced mod r; c_0 is the group secret, the randomness is the caller's).  For i = 1..n:
+ * out_sk32[i-1] = f(i) mod r (canonical, big-endian), out_vk65[i-1] = f(i) * g2;
+ * out_pk65 = c_0 * g2.  out_ok: n + 1 bytes, [0] for PK, [i] for share i; 0 (with 65 zero key
+ * bytes) where the scalar is 0 mod r.  1 <= k <= n <= 2048, else CBFT_EINVAL before any launch; a null
+ * pointer is CBFT_EINVAL with the outputs untouched.  Blocking. */
+int cbft_bls_keygen_threshold(cbft_ctx* ctx, const uint8_t* coeff32, uint32_t k, uint32_t n,
+                              uint8_t* out_sk32, uint8_t* out_vk65, uint8_t* out_pk65, uint8_t* out_ok);
 
 /* Sign a share: out37 = 4-byte big-endian id || sk * g1_map(msg) compressed, sk = 32 bytes
  * big-endian (< r) (IThresholdSigner::signData; BlsThresholdSigner.cpp:32-47). */
