@@ -174,6 +174,8 @@ ABI = [
      [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_uint32,
       ctypes.POINTER(ctypes.c_int)]),
     ("cbft_ecdsa_load_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _u32p]),
+    ("cbft_ecdsa_load_keys_curve", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, _u32p]),
     ("cbft_ecdsa_key_status", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     ("cbft_ecdsa_unload_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
     ("cbft_ecdsa_verify_batch", ctypes.c_int,
@@ -195,6 +197,9 @@ ABI = [
       ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_ecdsa_sign_kernel_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
 ]
+
+# cbft_ecdsa_load_keys_curve curves (include/cbft_hipcrypto.h, CBFT_CURVE_*)
+ECDSA_CURVES = {"secp256k1": 0, "p256": 1}
 
 # cbft_set_option options (include/cbft_hipcrypto.h, "tuning")
 OPT_LADDER_LANES = 1
@@ -525,13 +530,16 @@ class Context:
         return out.value
 
     # ------------------------------------------------------------------ ECDSA secp256k1 / SHA-256
-    def ecdsa_load_keys(self, keys) -> int:
-        """keys: 64-byte public keys (X || Y big-endian), a list of bytes or an (n, 64) uint8 array."""
+    def ecdsa_load_keys(self, keys, curve: str = "secp256k1") -> int:
+        """keys: 64-byte public keys (X || Y big-endian), a list of bytes or an (n, 64) uint8 array.
+        curve: "secp256k1" or "p256"; the table remembers it and every other ecdsa_* call follows."""
+        if curve not in ECDSA_CURVES:
+            raise ValueError(f"unknown ECDSA curve {curve!r}")
         k = _as_rows(keys, 64)
         buf = k if k.shape[0] else np.zeros((1, 64), np.uint8)
         tid = ctypes.c_uint32()
-        _check(self.lib.cbft_ecdsa_load_keys(self.handle, _ptr(buf), k.shape[0], ctypes.byref(tid)),
-               "cbft_ecdsa_load_keys")
+        _check(self.lib.cbft_ecdsa_load_keys_curve(self.handle, ECDSA_CURVES[curve], _ptr(buf), k.shape[0],
+                                                    ctypes.byref(tid)), "cbft_ecdsa_load_keys_curve")
         return tid.value
 
     def ecdsa_unload_keys(self, tid: int):

@@ -1,4 +1,6 @@
-// libcbft_hipcrypto, ECDSA secp256k1 / SHA-256 half of the C ABI (include/cbft_hipcrypto.h).
+// libcbft_hipcrypto, ECDSA secp256k1 / SHA-256 half of the C ABI (include/cbft_hipcrypto.h), and P-256 /
+// SHA-256 verification behind the same calls: a key table remembers its curve (cbft_ecdsa_load_keys_curve),
+// ids share one space, and every other call dispatches on the table's curve.
 //
 // Replaces concord::util::crypto::ECDSAVerifier (util/src/crypto_utils.cpp:34-64,231-236): one
 // verifier per key there; here a key table is loaded once (keys validated and their window tables
@@ -14,6 +16,7 @@
 #include <vector>
 
 #include "cbft_internal.h"
+#include "ecdsa_p256_verify.h"
 #include "ecdsa_verify.h"
 
 static_assert(CBFT_ECDSA_PUBLIC_KEY_BYTES == ECDSA_PUB_BYTES, "key size");
@@ -24,27 +27,35 @@ void cbft_ecdsa_release(cbft_ctx* c) {
   (void)hipDeviceSynchronize();  // device-path batches run on caller streams
   for (auto& kv : c->ecdsa_tables) kv.second.rec.release();
   c->ecdsa_tables.clear();
-  for (DevBuf* b : {&c->ecdsa.gtab, &c->ecdsa.sig, &c->ecdsa.kidx}) b->release();
+  for (DevBuf* b : {&c->ecdsa.gtab, &c->ecdsa.gtab_p256, &c->ecdsa.sig, &c->ecdsa.kidx}) b->release();
   c->ecdsa.scratch.release();
   c->ecdsa.timer.release();
 }
 
-// G's window table: the record of the key Q = G, built once per context by the key-load kernel
-static int ecdsa_gtab_locked(cbft_ctx* c) {
-  if (c->ecdsa.gtab.p) return CBFT_OK;
-  static const uint8_t g[ECDSA_PUB_BYTES] = ECDSA_G_BYTES;
+static hipError_t ecdsa_launch_keys(int curve, const uint8_t* d_pub, uint32_t nkeys, uint32_t* d_keys, hipStream_t s) {
+  return curve == CBFT_CURVE_P256 ? cbft_ecdsa_p256_launch_keys(d_pub, nkeys, d_keys, s)
+                                  : cbft_ecdsa_launch_keys(d_pub, nkeys, d_keys, s);
+}
+
+// G's window table: the record of the key Q = G, built once per context and curve by the key-load kernel
+static int ecdsa_gtab_locked(cbft_ctx* c, int curve) {
+  DevBuf& slot = curve == CBFT_CURVE_P256 ? c->ecdsa.gtab_p256 : c->ecdsa.gtab;
+  if (slot.p) return CBFT_OK;
+  static const uint8_t g_k1[ECDSA_PUB_BYTES] = ECDSA_G_BYTES;
+  static const uint8_t g_p256[ECDSA_PUB_BYTES] = ECDSA_P256_G_BYTES;
+  const uint8_t* g = curve == CBFT_CURVE_P256 ? g_p256 : g_k1;
   DevBuf pub, tab;
   hipError_t e = pub.reserve(ECDSA_PUB_BYTES);
   if (e == hipSuccess) e = tab.reserve(ECDSA_KEY_WORDS * sizeof(uint32_t));
   if (e == hipSuccess) e = hipMemcpyAsync(pub.p, g, ECDSA_PUB_BYTES, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = cbft_ecdsa_launch_keys(pub.as<uint8_t>(), 1, tab.as<uint32_t>(), c->stream);
+  if (e == hipSuccess) e = ecdsa_launch_keys(curve, pub.as<uint8_t>(), 1, tab.as<uint32_t>(), c->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   pub.release();
   if (e != hipSuccess) {
     tab.release();
     return cbft_fail(e, "ecdsa generator table", __FILE__, __LINE__);
   }
-  c->ecdsa.gtab = tab;
+  slot = tab;
   return CBFT_OK;
 }
 
@@ -52,9 +63,14 @@ static int ecdsa_launch_locked(cbft_ctx* c, EcdsaKeyTable& kt, const uint32_t* d
                                const uint8_t* d_msg, const uint64_t* d_off, const uint32_t* d_len, size_t n,
                                uint64_t* d_verdicts, hipStream_t s) {
   CBFT_HIP(c->ecdsa.scratch.acquire(cbft_ecdsa_scratch_words(n) * sizeof(uint32_t), s));
-  EcdsaBatch b{n, kt.rec.as<uint32_t>(), kt.nkeys, c->ecdsa.gtab.as<uint32_t>(), d_kidx, d_sig, d_msg, d_off, d_len};
+  const bool p256 = kt.curve == CBFT_CURVE_P256;
+  const DevBuf& gtab = p256 ? c->ecdsa.gtab_p256 : c->ecdsa.gtab;
+  EcdsaBatch b{n, kt.rec.as<uint32_t>(), kt.nkeys, gtab.as<uint32_t>(), d_kidx, d_sig, d_msg, d_off, d_len};
   CBFT_HIP(c->ecdsa.timer.begin(c->profiling, s));
-  CBFT_HIP(cbft_ecdsa_launch_verify(b, c->ecdsa.scratch.buf.as<uint32_t>(), d_verdicts, s));
+  if (p256)
+    CBFT_HIP(cbft_ecdsa_p256_launch_verify(b, c->ecdsa.scratch.buf.as<uint32_t>(), d_verdicts, s));
+  else
+    CBFT_HIP(cbft_ecdsa_launch_verify(b, c->ecdsa.scratch.buf.as<uint32_t>(), d_verdicts, s));
   CBFT_HIP(c->ecdsa.timer.end(c->profiling, s));
   CBFT_HIP(c->ecdsa.scratch.commit(s));
   return CBFT_OK;
@@ -64,21 +80,23 @@ extern "C" {
 
 // One device's key records under `want_id` (chosen by a multi-device parent, so every device
 // holds the table under the same id) or under the device's next id when want_id == 0.
-static int ecdsa_load_on(cbft_ctx* c, const uint8_t* pub, uint32_t nkeys, uint32_t want_id, uint32_t* out_id) {
+static int ecdsa_load_on(cbft_ctx* c, int curve, const uint8_t* pub, uint32_t nkeys, uint32_t want_id,
+                         uint32_t* out_id) {
   std::lock_guard<std::mutex> g(c->mu);
   if (want_id && c->ecdsa_tables.count(want_id)) return CBFT_EIO;
   CBFT_HIP(hipSetDevice(c->device));
-  const int grc = ecdsa_gtab_locked(c);
+  const int grc = ecdsa_gtab_locked(c, curve);
   if (grc) return grc;
   EcdsaKeyTable kt;
   kt.nkeys = nkeys;
+  kt.curve = curve;
   const size_t nk = std::max<uint32_t>(nkeys, 1);
   CBFT_HIP(kt.rec.reserve(nk * ECDSA_KEY_WORDS * sizeof(uint32_t)));
   if (nkeys) {
     DevBuf in;
     hipError_t e = in.reserve((size_t)nkeys * ECDSA_PUB_BYTES);
     if (e == hipSuccess) e = hipMemcpyAsync(in.p, pub, (size_t)nkeys * ECDSA_PUB_BYTES, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = cbft_ecdsa_launch_keys(in.as<uint8_t>(), nkeys, kt.rec.as<uint32_t>(), c->stream);
+    if (e == hipSuccess) e = ecdsa_launch_keys(curve, in.as<uint8_t>(), nkeys, kt.rec.as<uint32_t>(), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     in.release();
     if (e != hipSuccess) {
@@ -93,9 +111,14 @@ static int ecdsa_load_on(cbft_ctx* c, const uint8_t* pub, uint32_t nkeys, uint32
 }
 
 int cbft_ecdsa_load_keys(cbft_ctx* c, const uint8_t* pub, uint32_t nkeys, uint32_t* out_id) {
+  return cbft_ecdsa_load_keys_curve(c, CBFT_CURVE_SECP256K1, pub, nkeys, out_id);
+}
+
+int cbft_ecdsa_load_keys_curve(cbft_ctx* c, int curve, const uint8_t* pub, uint32_t nkeys, uint32_t* out_id) {
   if (!c || !out_id || (nkeys && !pub)) return CBFT_EINVAL;
+  if (curve != CBFT_CURVE_SECP256K1 && curve != CBFT_CURVE_P256) return CBFT_EINVAL;
   if (nkeys > CBFT_ECDSA_MAX_KEYS) return CBFT_E2BIG;
-  if (c->kids.empty()) return ecdsa_load_on(c, pub, nkeys, 0, out_id);
+  if (c->kids.empty()) return ecdsa_load_on(c, curve, pub, nkeys, 0, out_id);
   // every device, concurrently, under one id the parent allocates; a device that failed leaves
   // no table behind on the others (they unload theirs), so ids stay in step for later loads
   uint32_t id;
@@ -106,7 +129,7 @@ int cbft_ecdsa_load_keys(cbft_ctx* c, const uint8_t* pub, uint32_t nkeys, uint32
   std::vector<int> rcs(c->kids.size(), CBFT_OK);
   (void)for_each_kid(c, [&](size_t g) {
     uint32_t got = 0;
-    return rcs[g] = ecdsa_load_on(c->kids[g], pub, nkeys, id, &got);
+    return rcs[g] = ecdsa_load_on(c->kids[g], curve, pub, nkeys, id, &got);
   });
   int rc = CBFT_OK;
   for (int r : rcs)

@@ -237,6 +237,7 @@ struct RsaKeyTable {
 // validity) built on the GPU at load time (ecdsa_verify.h ECDSA_KEY_WORDS)
 struct EcdsaKeyTable {
   uint32_t nkeys = 0;
+  int curve = 0;  // CBFT_CURVE_*: which lane code built the records and verifies against them
   DevBuf rec;
 };
 
@@ -400,6 +401,7 @@ struct cbft_ctx {
   uint32_t next_ecdsa_id = 1;
   struct {
     DevBuf gtab;           // G's window table (the record of the key Q = G), built at the first load
+    DevBuf gtab_p256;      // the same for P-256's generator, built at the first P-256 load
     ScratchGuard scratch;  // the batch's digests (public)
     DevBuf sig, kidx;      // signatures / indices of a host-array batch
     KernelTimer timer;     // around the last ECDSA batch's kernels

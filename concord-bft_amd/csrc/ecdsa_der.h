@@ -1,0 +1,65 @@
+// Strict DER front end of the ECDSA verifiers that take OpenSSL-style signatures (host only, no
+// OpenSSL dependency): SEQUENCE { INTEGER r, INTEGER s } -> r || s, each left-padded to the
+// order's width, as the batch ABI takes them.
+//
+// Accepted is exactly what OpenSSL 3.0.2's ECDSA_verify lets through before it looks at the
+// curve: it parses with d2i_ECDSA_SIG, re-encodes with i2d_ECDSA_SIG and requires the same bytes
+// and no trailing ones, so only the canonical encoding passes: definite lengths in their shortest
+// form, integers with their shortest padding.  A negative INTEGER re-encodes to itself there and is
+// then refused by the range check 1 <= r, s; here it is refused at once, as is an integer wider
+// than the order (both are verdict false either way).
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+
+namespace ecdsa_der_detail {
+// a definite length in its shortest form at der[*pos]; advances *pos past it
+inline bool length(const uint8_t* der, size_t len, size_t* pos, size_t* out) {
+  if (*pos >= len) return false;
+  const uint8_t l0 = der[(*pos)++];
+  if (l0 < 0x80) {
+    *out = l0;
+    return true;
+  }
+  const size_t nb = l0 & 0x7F;
+  if (nb == 0 || nb > 4 || len - *pos < nb) return false;  // indefinite (BER), oversized, cut short
+  if (der[*pos] == 0) return false;                         // a leading zero byte: not the shortest form
+  size_t v = 0;
+  for (size_t i = 0; i < nb; i++) v = (v << 8) | der[(*pos)++];
+  if (v < 0x80) return false;  // the short form would have done
+  *out = v;
+  return true;
+}
+// a non-negative INTEGER with its shortest padding -> out[0 .. width), big-endian, left-padded
+inline bool integer(const uint8_t* der, size_t len, size_t* pos, size_t width, uint8_t* out) {
+  if (*pos >= len || der[(*pos)++] != 0x02) return false;
+  size_t n;
+  if (!length(der, len, pos, &n)) return false;
+  if (n == 0 || len - *pos < n) return false;
+  const uint8_t* b = der + *pos;
+  *pos += n;
+  if (b[0] & 0x80) return false;                             // negative
+  if (n > 1 && b[0] == 0 && !(b[1] & 0x80)) return false;    // a zero byte that no sign bit asks for
+  if (b[0] == 0) {  // the sign byte (or the value 0 itself)
+    b++;
+    n--;
+  }
+  if (n > width) return false;  // wider than the order
+  for (size_t i = 0; i < width - n; i++) out[i] = 0;
+  for (size_t i = 0; i < n; i++) out[width - n + i] = b[i];
+  return true;
+}
+}  // namespace ecdsa_der_detail
+
+// out_rs: 2 * order_bytes bytes.  false: not a canonical DER ECDSA signature over an order of that
+// width (out_rs unspecified); the verdict is then false.
+inline bool ecdsa_der_to_rs(const uint8_t* der, size_t len, size_t order_bytes, uint8_t* out_rs) {
+  using namespace ecdsa_der_detail;
+  if (!der || len < 2 || der[0] != 0x30) return false;
+  size_t pos = 1, body;
+  if (!length(der, len, &pos, &body)) return false;
+  if (len - pos != body) return false;  // cut short, or trailing bytes
+  if (!integer(der, len, &pos, order_bytes, out_rs)) return false;
+  if (!integer(der, len, &pos, order_bytes, out_rs + order_bytes)) return false;
+  return pos == len;  // nothing after s inside the SEQUENCE
+}

@@ -12,8 +12,10 @@
 //   HipRSAVerifier : IVerifier     RSASS<PKCS1v15, SHA256> with Crypto++ 8.2.0 semantics
 //                                  (util/src/crypto_utils.cpp:101-117), 2048-bit moduli
 //   HipECDSAVerifier : IVerifier   ECDSA / SHA-256 (Crypto++ ECDSA<ECP, SHA256>, crypto_utils.cpp:34-64):
-//                                  secp256k1 keys on the GPU with OpenSSL 3.0.2's verdicts, keys on
-//                                  other curves on the host OpenSSL
+//                                  secp256k1 and prime256v1 keys on the GPU with OpenSSL 3.0.2's verdicts,
+//                                  keys on other curves on the host OpenSSL
+//   HipP256PublicKey               ECDSA P-256 / SHA-256 with DER signatures, the shape of
+//                                  concord::util::openssl_utils::AsymmetricPublicKey (openssl_crypto.cpp)
 //   EdDSASigner : ISigner          Ed25519 signing: sign() on the host OpenSSL (one signature is
 //                                  latency-bound on any device); signBatch() on the GPU from
 //                                  CBFT_SIGN_GPU_MIN requests up (the pre-processing path signs one
@@ -145,12 +147,17 @@ class EcdsaEngine;  // per-process owner of the cbft_ctx and of the device ECDSA
 // arrays in to bitmap out, against a one-thread loop of OpenSSL ECDSA_do_verify.
 // Below it the items are verified on the host with OpenSSL, whose verdicts the GPU path reproduces.
 #define CBFT_ECDSA_GPU_MIN_DEFAULT 32
+// The same for prime256v1 (P-256) items ($CBFT_ECDSA_P256_GPU_MIN overrides), against a one-thread loop of
+// OpenSSL's P-256 ECDSA_do_verify, which is several times faster than its secp256k1: 128
+// (profiles/ecdsa_p256_verify.json "crossover").
+#define CBFT_ECDSA_P256_GPU_MIN_DEFAULT 128
 
 // ECDSA / SHA-256 in place of concord::util::crypto::ECDSAVerifier (Crypto++ ECDSA<ECP, SHA256>,
 // util/include/crypto_utils.hpp:57-77).  Signatures are r || s, each as long as the group order
 // (IEEE P1363, what Crypto++ reads and writes).  A secp256k1 key (the reference's default curve)
 // registers with the process's key table and is verified on the GPU from gpuMinBatch() items per
-// call up; a key on any other curve the host OpenSSL knows (KeyExchangeManager generates secp384r1
+// call up; a prime256v1 (P-256) key registers in a table of its own and goes to the GPU from
+// gpuMinBatchP256() items up; a key on any other curve the host OpenSSL knows (KeyExchangeManager generates secp384r1
 // keys) is verified with OpenSSL.
 class HipECDSAVerifier : public IVerifier {
  public:
@@ -170,9 +177,13 @@ class HipECDSAVerifier : public IVerifier {
   bool gpuCapable() const { return gpu_capable_; }
   uint32_t engineKeyIndex() const { return key_index_; }
   static size_t gpuMinBatch();
+  static size_t gpuMinBatchP256();
+  // CBFT_CURVE_* of a GPU-capable key (secp256k1 or prime256v1)
+  int curve() const { return curve_; }
   // Verifies every request whose verifier is a HipECDSAVerifier: the secp256k1 ones in one GPU
-  // batch when there are gpuMinBatch() or more of them, everything else on the host; out[i] =
-  // verdict of reqs[i] (false for other verifier types).
+  // batch when there are gpuMinBatch() or more of them, the prime256v1 ones in another when there are
+  // gpuMinBatchP256() or more of them, everything else on the host; out[i] = verdict of reqs[i] (false
+  // for other verifier types).
   static void verifyBatch(const std::vector<VerifyRequest>& reqs, std::vector<bool>& out);
 
  private:
@@ -181,8 +192,42 @@ class HipECDSAVerifier : public IVerifier {
   uint32_t sig_len_ = 0;
   bool gpu_capable_ = false;
   uint32_t key_index_ = 0;
+  int curve_ = 0;         // CBFT_CURVE_* when gpu_capable_
+  uint8_t pub_[64] = {0};  // X || Y of a GPU-capable key
   void* pkey_ = nullptr;  // EVP_PKEY* for the host path
   std::shared_ptr<EcdsaEngine> engine_;
+  friend class HipP256PublicKey;
+};
+
+// ECDSA P-256 / SHA-256 public key in the shape of concord::util::openssl_utils::AsymmetricPublicKey
+// (util/include/openssl_crypto.hpp): built from the serialised form "PUBLIC_KEY:secp256r1:<hex point>",
+// verifies DER-encoded signatures.  A thin adapter: csrc/ecdsa_der.h turns the signature into r || s
+// (anything but the canonical encoding is verdict false, as OpenSSL's ECDSA_verify has it), then the
+// HipECDSAVerifier path for a prime256v1 key.
+class HipP256PublicKey {
+ public:
+  // Throws std::invalid_argument unless `serialized` is PUBLIC_KEY:secp256r1: and a hex point on the curve.
+  explicit HipP256PublicKey(const std::string& serialized);
+  ~HipP256PublicKey();
+  HipP256PublicKey(const HipP256PublicKey&) = delete;
+  HipP256PublicKey& operator=(const HipP256PublicKey&) = delete;
+
+  bool verify(const std::string& message, const std::string& der_signature) const;
+  std::string serialize() const;  // PUBLIC_KEY:secp256r1:04<X><Y>, upper-case hex
+  const HipECDSAVerifier& verifier() const { return *verifier_; }
+
+  struct Request {
+    const HipP256PublicKey* key;
+    const char* data;
+    size_t dataLength;
+    const char* sig;  // DER
+    size_t sigLength;
+  };
+  // out[i] = verdict of reqs[i]; the parsed signatures go through HipECDSAVerifier::verifyBatch together
+  static void verifyBatch(const std::vector<Request>& reqs, std::vector<bool>& out);
+
+ private:
+  std::unique_ptr<HipECDSAVerifier> verifier_;
 };
 
 // Smallest secp256k1 HipECDSASigner::signBatch that goes to the GPU ($CBFT_ECDSA_SIGN_GPU_MIN
@@ -328,6 +373,12 @@ struct SignStats {
 SignStats ed25519SignStats();
 SignStats rsaSignStats();  // the same for HipRSASigner::signBatch
 SignStats ecdsaSignStats();  // the same for HipECDSASigner::signBatch
+// prime256v1 verification in HipECDSAVerifier::verifyBatch: GPU batches and their items, items verified on
+// the host below gpuMinBatchP256(), failed GPU calls (their items come out false)
+struct EcdsaP256VerifyStats {
+  uint64_t gpu_batches, gpu_items, host_items, gpu_errors;
+};
+EcdsaP256VerifyStats ecdsaP256VerifyStats();
 
 // Selects the GPU the engines open (default 0; $CBFT_DEVICE overrides).  Call before the first
 // verifier is constructed.

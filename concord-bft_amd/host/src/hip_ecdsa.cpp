@@ -5,6 +5,10 @@
 // its call site is reconfiguration_handler.cpp:332-338.  Key parsing here uses the host OpenSSL
 // (d2i_PUBKEY / PEM_read_bio_PUBKEY); secp256k1 batches of gpuMinBatch() items and more run on the
 // GPU, smaller ones and other curves on the host OpenSSL (the GPU path reproduces its verdicts).
+// prime256v1 (secp256r1, P-256) keys are GPU-capable too: they register in a table of their own in the
+// same engine and go to the GPU from gpuMinBatchP256() items up.  HipP256PublicKey is the shape of
+// concord::util::openssl_utils::AsymmetricPublicKey over such a key: DER signatures, undone by
+// csrc/ecdsa_der.h, then the same path.
 //
 // Signer: concord::util::crypto::ECDSASigner (crypto_utils.cpp:66-99), keyed from hex DER or PEM of an
 // EC private key.  secp256k1 keys sign with RFC 6979 nonces: sign() with the lane code of
@@ -27,6 +31,7 @@
 
 #include <openssl/crypto.h>
 
+#include "../../csrc/ecdsa_der.h"   // DER -> r || s for HipP256PublicKey
 #include "../../csrc/ecdsa_sign.h"  // the signing lane code, host build
 #include "cbft_hipcrypto.h"
 #include "hip_crypto.hpp"
@@ -76,6 +81,7 @@ const uint32_t* hostCombTable() {
   return tbl.data();
 }
 
+std::atomic<uint64_t> g_p256_gpu_batches{0}, g_p256_gpu_items{0}, g_p256_host_items{0}, g_p256_gpu_errors{0};
 std::atomic<uint64_t> g_sign_gpu_batches{0}, g_sign_gpu_items{0}, g_sign_host_items{0}, g_sign_gpu_errors{0};
 std::mutex g_sign_register_mu;
 
@@ -106,14 +112,16 @@ class EcdsaEngine {
   }
 
   // registration needs no GPU: the context is opened by the first batch
-  uint32_t registerKey(const uint8_t pub[64]) {
+  // curve: CBFT_CURVE_*; each curve has its own key set and device table, indices count per curve
+  uint32_t registerKey(int curve, const uint8_t pub[64]) {
     std::lock_guard<std::mutex> g(mu_);
+    KeySet& ks = sets_[curve];
     std::string k(reinterpret_cast<const char*>(pub), 64);
-    auto it = index_.find(k);
-    if (it != index_.end()) return it->second;
-    const uint32_t idx = (uint32_t)(pubs_.size() / 64);
-    pubs_.insert(pubs_.end(), pub, pub + 64);
-    index_.emplace(std::move(k), idx);
+    auto it = ks.index.find(k);
+    if (it != ks.index.end()) return it->second;
+    const uint32_t idx = (uint32_t)(ks.pubs.size() / 64);
+    ks.pubs.insert(ks.pubs.end(), pub, pub + 64);
+    ks.index.emplace(std::move(k), idx);
     return idx;
   }
 
@@ -128,18 +136,30 @@ class EcdsaEngine {
   }
 
   // one batch of 64-byte signatures; GPU failures become false verdicts and are counted
-  void verifyNoThrow(const std::vector<uint32_t>& kidx, const std::vector<uint8_t>& sig, const std::vector<uint8_t>& msg,
+  // returns false when the GPU call failed
+  bool verifyNoThrow(int curve, const std::vector<uint32_t>& kidx, const std::vector<uint8_t>& sig, const std::vector<uint8_t>& msg,
                      const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, std::vector<uint8_t>& bitmap) {
     try {
-      verify(kidx, sig, msg, off, len, bitmap);
+      verify(curve, kidx, sig, msg, off, len, bitmap);
+      return true;
     } catch (...) {
-      gpu_errors_++;
+      if (curve == CBFT_CURVE_P256)
+        g_p256_gpu_errors++;  // read by ecdsaP256VerifyStats()
+      else
+        gpu_errors_++;
       std::fill(bitmap.begin(), bitmap.end(), 0);
+      return false;
     }
   }
 
  private:
   static constexpr uint32_t kNoTable = 0;  // table ids start at 1
+  struct KeySet {  // one curve's registered keys and their device table
+    std::vector<uint8_t> pubs;
+    std::map<std::string, uint32_t> index;
+    uint32_t table = kNoTable;
+    uint32_t loaded = 0;
+  };
   EcdsaEngine() = default;
 
   void open() {
@@ -153,57 +173,56 @@ class EcdsaEngine {
     }
   }
 
-  void verify(const std::vector<uint32_t>& kidx, const std::vector<uint8_t>& sig, const std::vector<uint8_t>& msg,
+  void verify(int curve, const std::vector<uint32_t>& kidx, const std::vector<uint8_t>& sig, const std::vector<uint8_t>& msg,
               const std::vector<uint64_t>& off, const std::vector<uint32_t>& len, std::vector<uint8_t>& bitmap) {
     open();
+    KeySet& ks = sets_[curve];
     std::shared_lock<std::shared_mutex> rd(tbl_mu_);
     while (true) {
       {
         std::lock_guard<std::mutex> g(mu_);
-        if (loaded_ == pubs_.size() / 64 && table_ != kNoTable) break;
+        if (ks.loaded == ks.pubs.size() / 64 && ks.table != kNoTable) break;
       }
       rd.unlock();
-      refreshTable();  // builds beside the old table; verifies keep using it meanwhile
+      refreshTable(curve);  // builds beside the old table; verifies keep using it meanwhile
       rd.lock();
     }
-    const int rc = cbft_ecdsa_verify_batch(ctx_, table_, kidx.data(), sig.data(), msg.data(), off.data(), len.data(),
+    const int rc = cbft_ecdsa_verify_batch(ctx_, ks.table, kidx.data(), sig.data(), msg.data(), off.data(), len.data(),
                                            kidx.size(), bitmap.data());
     if (rc != CBFT_OK) fail("cbft_ecdsa_verify_batch", rc);
   }
 
   // Rebuild the device key table for the keys registered so far without blocking verifies (as
   // RsaEngine::refreshTable): records are 1 KB each and built by one kernel launch.
-  void refreshTable() {
+  void refreshTable(int curve) {
     std::lock_guard<std::mutex> b(build_mu_);
+    KeySet& ks = sets_[curve];
     std::vector<uint8_t> pubs;
     {
       std::lock_guard<std::mutex> g(mu_);
-      if (loaded_ == pubs_.size() / 64 && table_ != kNoTable) return;
-      pubs = pubs_;
+      if (ks.loaded == ks.pubs.size() / 64 && ks.table != kNoTable) return;
+      pubs = ks.pubs;
     }
     uint32_t id;
-    const int rc = cbft_ecdsa_load_keys(ctx_, pubs.data(), (uint32_t)(pubs.size() / 64), &id);
-    if (rc != CBFT_OK) fail("cbft_ecdsa_load_keys", rc);
+    const int rc = cbft_ecdsa_load_keys_curve(ctx_, curve, pubs.data(), (uint32_t)(pubs.size() / 64), &id);
+    if (rc != CBFT_OK) fail("cbft_ecdsa_load_keys_curve", rc);
     uint32_t old;
     {
       std::unique_lock<std::shared_mutex> wr(tbl_mu_);
       std::lock_guard<std::mutex> g(mu_);
-      old = table_;
-      table_ = id;
-      loaded_ = (uint32_t)(pubs.size() / 64);
+      old = ks.table;
+      ks.table = id;
+      ks.loaded = (uint32_t)(pubs.size() / 64);
     }
     if (old != kNoTable) cbft_ecdsa_unload_keys(ctx_, old);  // readers now see table_ = id
   }
 
   cbft_ctx* ctx_ = nullptr;
-  std::mutex mu_;             // guards ctx_ (opening), pubs_, index_, table_, loaded_
+  std::mutex mu_;             // guards ctx_ (opening) and sets_
   std::shared_mutex tbl_mu_;  // device table lifetime vs in-flight verifies
   std::mutex build_mu_;       // one table rebuild at a time
-  std::vector<uint8_t> pubs_;
-  std::map<std::string, uint32_t> index_;
-  uint32_t table_ = kNoTable;
-  uint32_t loaded_ = 0;
-  std::atomic<uint64_t> gpu_errors_{0};
+  KeySet sets_[2];            // by CBFT_CURVE_*
+  std::atomic<uint64_t> gpu_errors_{0};  // failed secp256k1 GPU calls (P-256 ones: g_p256_gpu_errors)
 };
 
 HipECDSAVerifier::HipECDSAVerifier(const std::string& str_pub_key, KeyFormat fmt) : key_str_(str_pub_key) {
@@ -216,7 +235,8 @@ HipECDSAVerifier::HipECDSAVerifier(const std::string& str_pub_key, KeyFormat fmt
             EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_EC_ORDER, &order) == 1;
   if (ok) sig_len_ = 2u * (uint32_t)BN_num_bytes(order);
   BN_free(order);
-  if (ok && std::strcmp(group, "secp256k1") == 0) {
+  const bool k1 = ok && std::strcmp(group, "secp256k1") == 0, p256 = ok && std::strcmp(group, "prime256v1") == 0;
+  if (k1 || p256) {
     uint8_t pub[64];
     ok = EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_EC_PUB_X, &x) == 1 &&
          EVP_PKEY_get_bn_param(k, OSSL_PKEY_PARAM_EC_PUB_Y, &y) == 1 && BN_bn2binpad(x, pub, 32) == 32 &&
@@ -224,8 +244,10 @@ HipECDSAVerifier::HipECDSAVerifier(const std::string& str_pub_key, KeyFormat fmt
     BN_free(x);
     BN_free(y);
     if (ok) {
+      curve_ = p256 ? CBFT_CURVE_P256 : CBFT_CURVE_SECP256K1;
       engine_ = EcdsaEngine::get();
-      key_index_ = engine_->registerKey(pub);
+      key_index_ = engine_->registerKey(curve_, pub);
+      std::memcpy(pub_, pub, 64);
       gpu_capable_ = true;
     }
   }
@@ -244,6 +266,15 @@ size_t HipECDSAVerifier::gpuMinBatch() {
     const char* e = std::getenv("CBFT_ECDSA_GPU_MIN");
     const long long x = e ? std::atoll(e) : 0;
     return x > 0 ? (size_t)x : (size_t)CBFT_ECDSA_GPU_MIN_DEFAULT;
+  }();
+  return v;
+}
+
+size_t HipECDSAVerifier::gpuMinBatchP256() {
+  static const size_t v = [] {
+    const char* e = std::getenv("CBFT_ECDSA_P256_GPU_MIN");
+    const long long x = e ? std::atoll(e) : 0;
+    return x > 0 ? (size_t)x : (size_t)CBFT_ECDSA_P256_GPU_MIN_DEFAULT;
   }();
   return v;
 }
@@ -284,9 +315,8 @@ bool HipECDSAVerifier::verify(const std::string& data, const std::string& sig) c
 
 void HipECDSAVerifier::verifyBatch(const std::vector<VerifyRequest>& reqs, std::vector<bool>& out) {
   out.assign(reqs.size(), false);
-  std::vector<size_t> pos;
+  std::vector<size_t> pos[2];  // GPU-capable requests by CBFT_CURVE_*
   std::shared_ptr<EcdsaEngine> engine;
-  size_t blob = 0;
   for (size_t i = 0; i < reqs.size(); i++) {
     auto v = dynamic_cast<const HipECDSAVerifier*>(reqs[i].verifier);
     if (!v) continue;
@@ -296,32 +326,114 @@ void HipECDSAVerifier::verifyBatch(const std::vector<VerifyRequest>& reqs, std::
     }
     if (reqs[i].sigLength != CBFT_ECDSA_SIGNATURE_BYTES || reqs[i].dataLength > 0xFFFFFF00u) continue;
     engine = v->engine_;
+    pos[v->curve_].push_back(i);
+  }
+  for (int curve = 0; curve < 2; curve++) {  // each curve's group goes to the GPU at its own minimum
+    const std::vector<size_t>& ps = pos[curve];
+    if (ps.empty()) continue;
+    const bool p256 = curve == CBFT_CURVE_P256;
+    const size_t n = ps.size();
+    if (n < (p256 ? gpuMinBatchP256() : gpuMinBatch())) {  // a host loop is faster than one GPU call
+      for (size_t i : ps)
+        out[i] = static_cast<const HipECDSAVerifier*>(reqs[i].verifier)
+                     ->verifyHost(reqs[i].data, reqs[i].dataLength, reqs[i].sig, reqs[i].sigLength);
+      if (p256) g_p256_host_items += n;
+      continue;
+    }
+    size_t blob = 0;
+    for (size_t i : ps) blob += reqs[i].dataLength;
+    std::vector<uint32_t> kidx(n), len(n);
+    std::vector<uint64_t> off(n);
+    std::vector<uint8_t> sig(n * CBFT_ECDSA_SIGNATURE_BYTES), msg(blob ? blob : 1), bitmap((n + 7) / 8);
+    size_t o = 0;
+    for (size_t j = 0; j < n; j++) {
+      const VerifyRequest& r = reqs[ps[j]];
+      kidx[j] = static_cast<const HipECDSAVerifier*>(r.verifier)->key_index_;
+      std::memcpy(&sig[CBFT_ECDSA_SIGNATURE_BYTES * j], r.sig, CBFT_ECDSA_SIGNATURE_BYTES);
+      off[j] = o;
+      len[j] = (uint32_t)r.dataLength;
+      if (r.dataLength) std::memcpy(&msg[o], r.data, r.dataLength);
+      o += r.dataLength;
+    }
+    const bool ran = engine->verifyNoThrow(curve, kidx, sig, msg, off, len, bitmap);
+    if (p256) {
+      if (ran) {  // a failed call is counted where it is caught (EcdsaEngine::verifyNoThrow)
+        g_p256_gpu_batches++;
+        g_p256_gpu_items += n;
+      }
+    }
+    for (size_t j = 0; j < n; j++) out[ps[j]] = (bitmap[j >> 3] >> (j & 7)) & 1;
+  }
+}
+
+EcdsaP256VerifyStats ecdsaP256VerifyStats() {
+  return EcdsaP256VerifyStats{g_p256_gpu_batches.load(), g_p256_gpu_items.load(), g_p256_host_items.load(), g_p256_gpu_errors.load()};
+}
+
+// ---- HipP256PublicKey ----------------------------------------------------------------------------
+namespace {
+const char kP256Prefix[] = "PUBLIC_KEY:secp256r1:";
+}
+
+HipP256PublicKey::HipP256PublicKey(const std::string& serialized) {
+  const size_t pl = sizeof kP256Prefix - 1;
+  std::vector<uint8_t> point;
+  if (serialized.compare(0, pl, kP256Prefix) != 0 || !fromHex(serialized.substr(pl), point) || point.empty())
+    throw std::invalid_argument("HipP256PublicKey: not PUBLIC_KEY:secp256r1:<hex point>");
+  // the point in any of the forms EC_POINT_point2hex writes (uncompressed, compressed, hybrid)
+  char group[] = "prime256v1";
+  OSSL_PARAM params[] = {OSSL_PARAM_construct_utf8_string(OSSL_PKEY_PARAM_GROUP_NAME, group, 0),
+                         OSSL_PARAM_construct_octet_string(OSSL_PKEY_PARAM_PUB_KEY, point.data(), point.size()),
+                         OSSL_PARAM_construct_end()};
+  EVP_PKEY_CTX* pc = EVP_PKEY_CTX_new_from_name(nullptr, "EC", nullptr);
+  EVP_PKEY* k = nullptr;
+  const bool ok = pc && EVP_PKEY_fromdata_init(pc) == 1 && EVP_PKEY_fromdata(pc, &k, EVP_PKEY_PUBLIC_KEY, params) == 1;
+  EVP_PKEY_CTX_free(pc);
+  unsigned char* der = nullptr;
+  const int n = ok ? i2d_PUBKEY(k, &der) : 0;
+  EVP_PKEY_free(k);
+  if (n <= 0) throw std::invalid_argument("HipP256PublicKey: not a point on secp256r1");
+  const std::string hex = toHex(der, (size_t)n);
+  OPENSSL_free(der);
+  verifier_.reset(new HipECDSAVerifier(hex, KeyFormat::HexaDecimalStrippedFormat));
+}
+
+HipP256PublicKey::~HipP256PublicKey() = default;
+
+std::string HipP256PublicKey::serialize() const {
+  // the uncompressed point in upper-case hex, as EC_POINT_point2hex writes it for this group
+  static const char* d = "0123456789ABCDEF";
+  std::string out = kP256Prefix;
+  out += "04";
+  for (int i = 0; i < 64; i++) {
+    out += d[verifier_->pub_[i] >> 4];
+    out += d[verifier_->pub_[i] & 15];
+  }
+  return out;
+}
+
+bool HipP256PublicKey::verify(const std::string& message, const std::string& der_signature) const {
+  std::vector<Request> r{{this, message.data(), message.size(), der_signature.data(), der_signature.size()}};
+  std::vector<bool> out;
+  verifyBatch(r, out);
+  return out[0];
+}
+
+void HipP256PublicKey::verifyBatch(const std::vector<Request>& reqs, std::vector<bool>& out) {
+  out.assign(reqs.size(), false);
+  std::vector<uint8_t> rs(reqs.size() * 64);
+  std::vector<VerifyRequest> vr;
+  std::vector<size_t> pos;
+  for (size_t i = 0; i < reqs.size(); i++) {
+    if (!reqs[i].key) continue;
+    if (!ecdsa_der_to_rs(reinterpret_cast<const uint8_t*>(reqs[i].sig), reqs[i].sigLength, 32, &rs[64 * i])) continue;
+    vr.push_back({reqs[i].key->verifier_.get(), reqs[i].data, reqs[i].dataLength,
+                  reinterpret_cast<const char*>(&rs[64 * i]), 64});
     pos.push_back(i);
-    blob += reqs[i].dataLength;
   }
-  if (pos.empty()) return;
-  const size_t n = pos.size();
-  if (n < gpuMinBatch()) {  // a host loop is faster than one GPU call
-    for (size_t i : pos)
-      out[i] = static_cast<const HipECDSAVerifier*>(reqs[i].verifier)
-                   ->verifyHost(reqs[i].data, reqs[i].dataLength, reqs[i].sig, reqs[i].sigLength);
-    return;
-  }
-  std::vector<uint32_t> kidx(n), len(n);
-  std::vector<uint64_t> off(n);
-  std::vector<uint8_t> sig(n * CBFT_ECDSA_SIGNATURE_BYTES), msg(blob ? blob : 1), bitmap((n + 7) / 8);
-  size_t o = 0;
-  for (size_t j = 0; j < n; j++) {
-    const VerifyRequest& r = reqs[pos[j]];
-    kidx[j] = static_cast<const HipECDSAVerifier*>(r.verifier)->key_index_;
-    std::memcpy(&sig[CBFT_ECDSA_SIGNATURE_BYTES * j], r.sig, CBFT_ECDSA_SIGNATURE_BYTES);
-    off[j] = o;
-    len[j] = (uint32_t)r.dataLength;
-    if (r.dataLength) std::memcpy(&msg[o], r.data, r.dataLength);
-    o += r.dataLength;
-  }
-  engine->verifyNoThrow(kidx, sig, msg, off, len, bitmap);
-  for (size_t j = 0; j < n; j++) out[pos[j]] = (bitmap[j >> 3] >> (j & 7)) & 1;
+  std::vector<bool> got;
+  HipECDSAVerifier::verifyBatch(vr, got);
+  for (size_t j = 0; j < pos.size(); j++) out[pos[j]] = got[j];
 }
 
 // ---- HipECDSASigner ------------------------------------------------------------------------------

@@ -616,6 +616,17 @@ int cbft_bls_sum_keys_batch(cbft_ctx* ctx, uint32_t keyset, const uint8_t* signe
  * >= p or off the curve ((0, 0) included) is accepted into the table and every signature under it
  * verifies false (cbft_ecdsa_key_status). */
 int cbft_ecdsa_load_keys(cbft_ctx* ctx, const uint8_t* pub, uint32_t nkeys, uint32_t* out_key_table_id);
+/* The same for a named curve.  CBFT_CURVE_P256 is NIST P-256 (secp256r1, prime256v1) with SHA-256: what
+ * concord::util::openssl_utils::AsymmetricPublicKey verifies through OpenSSL EVP (util/src/openssl_crypto.cpp),
+ * with the signature as r || s here (csrc/ecdsa_der.h undoes the DER form on the host); verdicts are those of
+ * OpenSSL 3.0.2 ECDSA_do_verify on prime256v1 (tests/golden/ecdsa_p256_vectors.json, restated in
+ * tests/p256_ref.py).  A key with x = 0 is on P-256 and usable.  A table remembers its curve, ids share one
+ * space, and key_status, unload_keys, verify_batch, verify_batch_device and kernel_ms work on either kind of
+ * table; cbft_ecdsa_load_keys is curve 0.  An unknown curve is CBFT_EINVAL. */
+#define CBFT_CURVE_SECP256K1 0
+#define CBFT_CURVE_P256 1
+int cbft_ecdsa_load_keys_curve(cbft_ctx* ctx, int curve, const uint8_t* pub, uint32_t nkeys,
+                               uint32_t* out_key_table_id);
 /* out_ok: nkeys bytes, 1 = the key is usable */
 int cbft_ecdsa_key_status(cbft_ctx* ctx, uint32_t key_table_id, uint8_t* out_ok);
 int cbft_ecdsa_unload_keys(cbft_ctx* ctx, uint32_t key_table_id);
