@@ -653,7 +653,7 @@ __global__ void __launch_bounds__(CBFT_VERIFY_BLOCK, CBFT_LADDER_MIN_WAVES)
 // product tree of round 5 put 6 product pairs and the slots one after another behind the
 // inversion): 35.4-35.9 us against 38.3 (same box, ladder_probe events, profiles/ab/r06/).  K = 2
 // from 16K signatures (512 blocks at 64K: the finish co-runs with the other streams' ladders,
-// whose 1,024 blocks of 36 KB fill a 64K batch's LDS, and a block's 9.2 KB fits beside them), K = 1
+// whose 1,024 blocks of 22 KB take 90 KB of a CU's 160 KB, and a block's 9.2 KB fits beside them), K = 1
 // below.
 // ---------------------------------------------------------------------------------------
 #define FINISH_BLOCK 128
@@ -1385,16 +1385,36 @@ __global__ void __launch_bounds__(SMALL3_BLOCK) ed25519_small3_kernel(const Ed25
 // q*nper + nper - 1, nper = ceil(positions / 2)), one DPP combine.  Per signature that is
 // 2 x (16 x 7M + 8M) = 240 lane-M at the default geometry against 4 x (8 x 7M + 17M) = 292 for
 // the quad form (whose two combine levels are a quarter of a lane's work), at 2 waves per SIMD
-// for a 64K batch instead of 4 (256 VGPRs per lane; gfx950 issues the mad / 64-bit mix ~9 %
-// slower per instruction at 2 waves than at 4: tools/microbench/intrate2.hip).  The lower
-// occupancy buys LDS for a second entry stage: entries jj+1 and jj+2 are in flight while
-// addition jj runs, so the key-table / B-table reads (random over tens of GB) stay hidden.
-// The two recoded scalars sit in LDS ([word][lane]) and each digit is extracted right before
-// its entry is requested.
+// for a 64K batch instead of 4.
+//
+// ONE 7 KB entry stage per wave.  Step jj waits for entry jj (vmcnt(0)), moves it into VGPRs (seven
+// ds_read_b128, lgkmcnt(0)) and only then requests entry jj+1 into the same stage: the request has
+// the whole addition (7 M, ~6 us at the headline's rate) to land, against 1-2 us of loaded HBM
+// latency, so the key-table / B-table reads (random over tens of GB) stay hidden without a second
+// stage.  Against two stages the step loop loses 10 instructions and the kernel 3 VGPRs, and a wave
+// holds 11,264 B of LDS (stage + 4 KB of recoded scalars) instead of 18,432.  The two recoded
+// scalars sit in LDS ([word][lane]) and each digit is extracted right before its entry is requested.
+//
+// Occupancy.  The kernel uses 153 VGPRs (the fold constants 1216 and 9728 ride in SGPRs), so with
+// 22,528 B per 128-lane group neither registers nor LDS would stop a third wave per SIMD, and
+// tools/microbench/intrate2.hip prices the mad + and mix 22 % cheaper at three waves than at two.
+// Measured in the three-stream headline it is the other way round: three ladder waves (480 of a
+// SIMD's 512 registers) leave no room for a hash or finish wave beside them, and the step is 4 %
+// SLOWER at either group size (64-lane groups also 19 % slower alone: the 2,048 one-wave groups of
+// a 64K batch do not spread two to a SIMD).  So the kernel is held at two waves per SIMD
+// (COMB2_WAVES), and the single stage alone is kept: isolated ladder -3.5 %, headline step -2.8 %
+// (DESIGN section 28).
 // ---------------------------------------------------------------------------------------
-#define COMB2_BLOCK 128
+#ifndef COMB2_BLOCK
+#define COMB2_BLOCK 128  // 64 or 128: no barrier, each wave owns its stage and its columns of sc
+#endif
 #define COMB2_MAX_STEPS 24  // additions per lane: radix-2^8 keys + radix-2^16 B = 48 positions
-#define COMB2_MIN_WAVES 2
+// Waves per SIMD, as both bounds of amdgpu_waves_per_eu: 2 pads the allocation to 169 VGPRs, which
+// is what holds a third wave off (a minimum alone leaves the 153 in use, and three waves fit); 3
+// allocates the 153.
+#ifndef COMB2_WAVES
+#define COMB2_WAVES 2
+#endif
 
 // Lane role of a pair (q = threadIdx.x & 1) as a mask LLVM cannot see through: all ones in lane 1.
 // With plain ternaries on q it would merge the limb-wise selects into divergent branches (as in
@@ -1500,7 +1520,7 @@ __device__ __forceinline__ void pair_combine_split(ge_p3& P, uint32_t q) {
   fe_dpp_quad<0xB1>(P.Z, r3);
 }
 
-__global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
+__global__ void __launch_bounds__(COMB2_BLOCK) __attribute__((amdgpu_waves_per_eu(COMB2_WAVES, COMB2_WAVES)))
     ed25519_comb2_ladder_kernel(const Ed25519Batch b, const uint32_t* h_soa, const uint32_t* btbl,
                                 const CombLadder cl, uint32_t* xyz_soa) {
   const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1515,7 +1535,7 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
   // 16 as ceil(32/2) at the default 20 + 12 positions.
   const uint32_t naper = (na + 1u) >> 1, nbper = (nb + 1u) >> 1;
   const uint32_t nper = naper + nbper;
-  __shared__ uint4 stage[COMB2_BLOCK / 64][2][7][64];  // per wave: two lane-linear 7 KB entry images
+  __shared__ uint4 stage[COMB2_BLOCK / 64][7][64];  // per wave: one lane-linear 7 KB entry image
   __shared__ uint32_t sc[16][COMB2_BLOCK];              // h + offA (words 0..7), S + offB (8..15)
   {
     uint32_t hs[8], ss[8];
@@ -1562,30 +1582,25 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
   };
   // wv through readfirstlane: the stage addresses of the entry requests (M0) stay on the scalar unit
   const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), ln = threadIdx.x & 63u;
-  auto request = [&](uint32_t slot, const uint32_t* e) {
+  auto request = [&](const uint32_t* e) {
 #pragma unroll
     for (int c = 0; c < 7; c++)
-      __builtin_amdgcn_global_load_lds(e + 4 * c, (__attribute__((address_space(3))) void*)&stage[wv][slot][c][0], 16,
-                                       0, 0);
+      __builtin_amdgcn_global_load_lds(e + 4 * c, (__attribute__((address_space(3))) void*)&stage[wv][c][0], 16, 0, 0);
   };
   ge_p3 P;
   ge_p3_0(P);
-  int dcur = digit(0), dnext = digit(1);
-  request(0, entry(0, dcur));
-  if (nper > 1u) request(1, entry(1, dnext));
+  int dcur = digit(0);
+  request(entry(0, dcur));
 #pragma nounroll
   for (uint32_t jj = 0; jj < nper; jj++) {
-    const uint32_t slot = jj & 1u;
-    if (jj + 1u < nper)
-      asm volatile("s_waitcnt vmcnt(7)" ::: "memory");  // entry jj landed; jj + 1 may still fly
-    else
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    // The stage is read with asm ds_reads: the compiler would otherwise see LDS reads after
-    // global_load_lds writes and wait for ALL of them (vmcnt(0)), serialising the two stages.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // entry jj landed in the stage
+    // The stage is read with asm ds_reads and explicit waits: the one stage is safe only in the order
+    // land (vmcnt) -> read into VGPRs (lgkmcnt) -> request the next entry, and the compiler must not
+    // move a request above the reads or fold the waits into others.
     uint32_t ew[28];
     {
       typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-      const uint32_t addr = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) uint4*)&stage[wv][slot][0][ln]);
+      const uint32_t addr = (uint32_t)(uintptr_t)((__attribute__((address_space(3))) uint4*)&stage[wv][0][ln]);
       u32x4 v[7];
 #define COMB2_DS_READ(c) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v[c]) : "v"(addr), "i"((c) * 1024))
       COMB2_DS_READ(0);
@@ -1596,7 +1611,7 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
       COMB2_DS_READ(5);
       COMB2_DS_READ(6);
 #undef COMB2_DS_READ
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // entry jj is in VGPRs: its stage is free
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // entry jj is in VGPRs: the stage is free
 #pragma unroll
       for (int c = 0; c < 7; c++) {
         ew[4 * c] = v[c].x;
@@ -1606,10 +1621,9 @@ __global__ void __launch_bounds__(COMB2_BLOCK, COMB2_MIN_WAVES)
       }
     }
     const bool neg = dcur < 0;
-    dcur = dnext;
-    if (jj + 2u < nper) {
-      dnext = digit(jj + 2u);
-      request(slot, entry(jj + 2u, dnext));
+    if (jj + 1u < nper) {  // the request has this whole step (7 M) to land
+      dcur = digit(jj + 1u);
+      request(entry(jj + 1u, dcur));
     }
     if (jj == 0) {
       // The lane's first addition starts from the identity: O + (x, y) needs no product but T.

@@ -189,7 +189,7 @@ def fold_wrapper(n):
         ins += [f"[{nm(p, 'a', k)}] \"v\"(a{sfx(p)}.v[{k}])" for k in range(9)]
         ins += [f"[{nm(p, 'b', k)}] \"v\"(b{sfx(p)}.v[{k}])" for k in range(9)]
         clob += [f"\"v{b + h}\"" for b in hb for h in (0, 1)]
-    ins += ["[k1216] \"v\"(1216u)", "[k9728] \"v\"(9728u)"]
+    ins += ["[k1216] \"s\"(1216u)", "[k9728] \"s\"(9728u)"]
     decl = "  fe " + ", ".join(f"o{sfx(p)}" for p in ps) + ";\n"
     decl += "  uint64_t cc, " + ", ".join(f"acc{sfx(p)}" for p in ps) + ";\n"
     macro = "CBFT_FE_MULF_ASM" if n is None else f"CBFT_FE_MULF{n}_ASM"

@@ -1,6 +1,6 @@
 // gfx950 issue-rate microbenchmark, part 2: the 64-bit integer helpers the compiler emits in the
 // field multiply (v_lshrrev_b64, v_lshl_add_u64), the 32-bit glue (and, alignbit, add3, cndmask),
-// mixes of v_mad_u64_u32 with 32-bit glue (do they overlap?), and the mad rate at 1/2/4/8 waves
+// mixes of v_mad_u64_u32 with 32-bit glue (do they overlap?), and the mad rate at 1/2/3/4/8 waves
 // per SIMD with and without instruction-level parallelism inside the wave.
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -134,7 +134,7 @@ int main() {
   int clk = 0;
   hipDeviceGetAttribute(&clk, hipDeviceAttributeClockRate, 0);
   printf("clock attr kHz=%d; wave-instr cycles per SIMD assume 2.4 GHz\n", clk);
-  for (int wps : {1, 2, 4, 8, 16}) {
+  for (int wps : {1, 2, 3, 4, 8, 16}) {
     const int blocks = 256 * wps;  // 4 waves per block, 1024 SIMDs: wps waves per SIMD
     for (auto& k : ks) {
       float ms = 0;
