@@ -12,8 +12,8 @@ ORACLE_LIB := oracle/libcbft_oracle.so
 # host SIMD emulation of the same source is exact).  Costs one v_mov_dpp per move.
 ROWFLAGS := -mllvm -amdgpu-dpp-combine=false
 
-.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim bls_combine_shim bls_keygen_shim sha512_shim ecdsa_shim ecdsa_sign_shim ecdsa_p256_shim host_util_test sanitize selftest
-all: lib oracle cpu host shim fe_row_shim bls_sign_shim bls_combine_shim bls_keygen_shim sha512_shim ecdsa_shim ecdsa_sign_shim ecdsa_p256_shim host_util_test selftest
+.PHONY: all lib oracle clean shim fe_row_shim bls_sign_shim bls_combine_shim bls_keygen_shim sha512_shim ecdsa_shim ecdsa_sign_shim ecdsa_p256_shim ecdsa_p256_sign_shim host_util_test sanitize selftest
+all: lib oracle cpu host shim fe_row_shim bls_sign_shim bls_combine_shim bls_keygen_shim sha512_shim ecdsa_shim ecdsa_sign_shim ecdsa_p256_shim ecdsa_p256_sign_shim host_util_test selftest
 
 lib: $(LIB)
 
@@ -114,13 +114,18 @@ ECDSA_SIGN_DEPS := $(CSRC)/ecdsa_sign.h $(ECDSA_DEPS)
 $(CSRC)/ecdsa_sign.o: $(CSRC)/ecdsa_sign.hip $(ECDSA_SIGN_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(CSRC)/cbft_ecdsa_sign.o: $(CSRC)/cbft_ecdsa_sign.cpp $(INTERNAL_DEPS) $(ECDSA_SIGN_DEPS)
+# ECDSA P-256 signing: its own lane code and object (constant-time; no other kernel is touched)
+ECDSA_P256_SIGN_DEPS := $(CSRC)/ecdsa_p256_sign.h $(CSRC)/ecdsa_sign.h $(ECDSA_P256_DEPS)
+$(CSRC)/ecdsa_p256_sign.o: $(CSRC)/ecdsa_p256_sign.hip $(ECDSA_P256_SIGN_DEPS)
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+$(CSRC)/cbft_ecdsa_sign.o: $(CSRC)/cbft_ecdsa_sign.cpp $(INTERNAL_DEPS) $(ECDSA_SIGN_DEPS) $(ECDSA_P256_SIGN_DEPS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(CSRC)/cbft_bls.o: $(CSRC)/cbft_bls.cpp $(INTERNAL_DEPS) $(CSRC)/bls_kernels.h
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
-$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/bls_combine_batch.o $(CSRC)/cbft_bls_combine_batch.o $(CSRC)/bls_multisig_batch.o $(CSRC)/cbft_bls_multisig_batch.o $(CSRC)/bls_keygen_batch.o $(CSRC)/cbft_bls_keygen.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o $(CSRC)/ecdsa_sign.o $(CSRC)/cbft_ecdsa_sign.o $(CSRC)/ecdsa_p256_verify.o
+$(LIB): $(CSRC)/ed25519_verify.o $(CSRC)/cbft_hipcrypto.o $(CSRC)/bls_kernels.o $(CSRC)/bls_msm_row.o $(CSRC)/bls_pairing.o $(CSRC)/bls_keys.o $(CSRC)/cbft_bls.o $(CSRC)/rsa_verify.o $(CSRC)/cbft_rsa.o $(CSRC)/ed25519_sign.o $(CSRC)/cbft_ed25519_sign.o $(CSRC)/rsa_sign.o $(CSRC)/cbft_rsa_sign.o $(CSRC)/bls_sign_batch.o $(CSRC)/cbft_bls_sign.o $(CSRC)/bls_verify_batch.o $(CSRC)/cbft_bls_verify_batch.o $(CSRC)/bls_combine_batch.o $(CSRC)/cbft_bls_combine_batch.o $(CSRC)/bls_multisig_batch.o $(CSRC)/cbft_bls_multisig_batch.o $(CSRC)/bls_keygen_batch.o $(CSRC)/cbft_bls_keygen.o $(CSRC)/ecdsa_verify.o $(CSRC)/cbft_ecdsa.o $(CSRC)/ecdsa_sign.o $(CSRC)/cbft_ecdsa_sign.o $(CSRC)/ecdsa_p256_verify.o $(CSRC)/ecdsa_p256_sign.o
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 
 oracle: $(ORACLE_LIB)
@@ -153,6 +158,12 @@ cpu: $(CPU_ECDSA_SIGN_LIB)
 $(CPU_ECDSA_SIGN_LIB): tools/cpu_baseline/openssl_ecdsa_sign.c
 	gcc -O2 -std=gnu11 -fPIC -shared -Wall -Wno-deprecated-declarations -o $@ $< -lcrypto -lpthread
 
+# the ECDSA P-256 signing host baseline of tools/ecdsa_p256_sign_bench.py (threads of ECDSA_do_sign on prime256v1)
+CPU_P256_SIGN_LIB := tools/cpu_baseline/libcbft_cpu_openssl_ecdsa_p256_sign.so
+cpu: $(CPU_P256_SIGN_LIB)
+$(CPU_P256_SIGN_LIB): tools/cpu_baseline/openssl_ecdsa_p256_sign.c
+	gcc -O2 -std=gnu11 -fPIC -shared -Wall -Wno-deprecated-declarations -o $@ $< -lcrypto -lpthread
+
 # C++ plugin layer.  Product sources (concord::hip, BLS::Hip) compile against the reference's own
 # headers in an integration build (tests/test_reference_boundary.py) and here against the
 # restatements in ref_mirror/ (the reference's util / bftengine / threshsign libraries need
@@ -163,8 +174,8 @@ HOST_SRC := $(HOST_DIR)/src/hip_ed25519.cpp $(HOST_DIR)/src/hip_rsa.cpp $(HOST_D
 MIRROR_SRC := $(wildcard $(HOST_DIR)/ref_mirror/src/*.cpp)
 HOST_INC := -Iinclude -I$(HOST_DIR)/include -I$(HOST_DIR)/ref_mirror/include -DCBFT_WITH_CLIENT_KEYS_MAP
 HOST_HDRS := $(wildcard $(HOST_DIR)/include/*.hpp $(HOST_DIR)/include/threshsign/*.hpp $(HOST_DIR)/ref_mirror/include/*.hpp $(HOST_DIR)/ref_mirror/include/threshsign/*.h)
-host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_bls_combine_host tests/cpp/test_bls_combine_plan_san tests/cpp/test_bls_multisig_host tests/cpp/test_bls_multisig_plan_san tests/cpp/test_bls_keygen_host tests/cpp/test_bls_keygen_san tests/cpp/test_ecdsa_host tests/cpp/test_ecdsa_sign_host tests/cpp/test_ecdsa_p256_host tests/cpp/test_ecdsa_p256_host_san tools/host_bench
-$(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB) $(ECDSA_SIGN_DEPS) $(CSRC)/ecdsa_der.h
+host: $(HOST_LIB) tests/cpp/test_host tests/cpp/test_bls_host tests/cpp/test_sign_host tests/cpp/test_rsa_sign_host tests/cpp/test_bls_sign_host tests/cpp/test_bls_verify_host tests/cpp/test_bls_combine_host tests/cpp/test_bls_combine_plan_san tests/cpp/test_bls_multisig_host tests/cpp/test_bls_multisig_plan_san tests/cpp/test_bls_keygen_host tests/cpp/test_bls_keygen_san tests/cpp/test_ecdsa_host tests/cpp/test_ecdsa_sign_host tests/cpp/test_ecdsa_p256_host tests/cpp/test_ecdsa_p256_host_san tests/cpp/test_ecdsa_p256_sign_host tests/cpp/test_ecdsa_p256_sign_host_san tools/host_bench
+$(HOST_LIB): $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB) $(ECDSA_SIGN_DEPS) $(ECDSA_P256_SIGN_DEPS) $(CSRC)/ecdsa_der.h
 	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas $(HOST_INC) -o $@ $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN'
 tests/cpp/test_host: tests/cpp/test_host.cpp $(HOST_LIB)
 	g++ -O2 -std=c++17 -Wall -DCONCORD_BFT_TESTING $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
@@ -214,6 +225,14 @@ tests/cpp/test_ecdsa_p256_host: tests/cpp/test_ecdsa_p256_host.cpp $(HOST_LIB)
 # the same test with the host sources compiled in under ASan + UBSan, for its --no-gpu mode (key parsing, the DER
 # front end, the host path; run by tests/test_cpp_ecdsa_p256_host.py as a stand-alone program, never loaded into python)
 tests/cpp/test_ecdsa_p256_host_san: tests/cpp/test_ecdsa_p256_host.cpp $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB) $(CSRC)/ecdsa_der.h
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -Wno-deprecated-declarations $(HOST_INC) -o $@ $< $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+tests/cpp/test_ecdsa_p256_sign_host: tests/cpp/test_ecdsa_p256_sign_host.cpp $(HOST_LIB)
+	g++ -O2 -std=c++17 -Wall -Wno-deprecated-declarations $(HOST_INC) -o $@ $< -Lconcord-bft_amd -lcbft_host -lcbft_hipcrypto -lcrypto -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
+
+# the same test with the host sources compiled in under ASan + UBSan, for its --no-gpu mode (key parsing, the lane code
+# on the host, the DER writer; run by tests/test_cpp_ecdsa_p256_sign_host.py as a stand-alone program, never loaded into python)
+tests/cpp/test_ecdsa_p256_sign_host_san: tests/cpp/test_ecdsa_p256_sign_host.cpp $(HOST_SRC) $(MIRROR_SRC) $(HOST_HDRS) $(LIB) $(ECDSA_P256_SIGN_DEPS) $(CSRC)/ecdsa_der.h
 	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -Wno-deprecated-declarations $(HOST_INC) -o $@ $< $(HOST_SRC) $(MIRROR_SRC) -Lconcord-bft_amd -lcbft_hipcrypto -lcrypto -lpthread -Wl,-rpath,'$$ORIGIN/../../concord-bft_amd'
 
 tests/cpp/test_ecdsa_sign_host: tests/cpp/test_ecdsa_sign_host.cpp $(HOST_LIB)
@@ -307,6 +326,17 @@ $(ECDSA_P256_SHIM): tests/cpp/ecdsa_p256_shim.cpp $(ECDSA_P256_DEPS) $(CSRC)/ecd
 $(ECDSA_P256_SHIM_SAN): tests/cpp/ecdsa_p256_shim.cpp $(ECDSA_P256_DEPS) $(CSRC)/ecdsa_der.h
 	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DECDSA_P256_SHIM_MAIN -I$(CSRC) -o $@ $<
 
+# host build of the ECDSA P-256 signing lane code (ecdsa_p256_sign.h) and the DER writer (ecdsa_der.h) for
+# tests/test_ecdsa_p256_sign_cpu.py, and the same source as a stand-alone program under ASan + UBSan (run by that
+# test, never loaded into python)
+ECDSA_P256_SIGN_SHIM := tests/cpp/libecdsa_p256_sign_shim.so
+ECDSA_P256_SIGN_SHIM_SAN := tests/cpp/ecdsa_p256_sign_shim_san
+ecdsa_p256_sign_shim: $(ECDSA_P256_SIGN_SHIM) $(ECDSA_P256_SIGN_SHIM_SAN)
+$(ECDSA_P256_SIGN_SHIM): tests/cpp/ecdsa_p256_sign_shim.cpp $(ECDSA_P256_SIGN_DEPS) $(CSRC)/ecdsa_der.h
+	g++ -O2 -std=c++17 -fPIC -shared -Wall -Wno-unknown-pragmas -I$(CSRC) -o $@ $< -lpthread
+$(ECDSA_P256_SIGN_SHIM_SAN): tests/cpp/ecdsa_p256_sign_shim.cpp $(ECDSA_P256_SIGN_DEPS) $(CSRC)/ecdsa_der.h
+	g++ -O1 -g -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -Wall -Wno-unknown-pragmas -DECDSA_P256_SIGN_SHIM_MAIN -I$(CSRC) -o $@ $< -lpthread
+
 # the front ends' HIP-free helpers (cbft_host_util.h) as a stand-alone program under ASan + UBSan
 # (run by tests/test_host_util_cpu.py, never loaded into python)
 HOST_UTIL_TEST := tests/cpp/host_util_test
@@ -357,6 +387,11 @@ FE25519_SELFTEST := tests/hip/libfe25519_selftest.so
 ECDSA_SIGN_SELFTEST := tests/hip/libecdsa_sign_selftest.so
 BLS_KEYGEN_SELFTEST := tests/hip/libbls_keygen_selftest.so
 ECDSA_P256_SELFTEST := tests/hip/libecdsa_p256_selftest.so
+ECDSA_P256_SIGN_SELFTEST := tests/hip/libecdsa_p256_sign_selftest.so
+selftest: $(ECDSA_P256_SIGN_SELFTEST)
+# test-only device harness of the ECDSA P-256 signing lane code, one function per launch (tests/test_ecdsa_p256_sign_gpu.py)
+$(ECDSA_P256_SIGN_SELFTEST): tests/hip/ecdsa_p256_sign_selftest.hip $(CSRC)/ecdsa_p256_sign.hip $(ECDSA_P256_SIGN_DEPS)
+	$(HIPCC) $(HIPFLAGS) -shared -o $@ $<
 selftest: $(SELFTEST) $(SIGN_SELFTEST) $(RSA_SIGN_SELFTEST) $(BLS_SIGN_SELFTEST) $(BLS_VERIFY_SELFTEST) $(BLS_COMBINE_SELFTEST) $(FE25519_SELFTEST) $(ECDSA_SIGN_SELFTEST) $(BLS_KEYGEN_SELFTEST) $(ECDSA_P256_SELFTEST)
 # test-only device harness of the ECDSA P-256 field, scalar and point lane code, one function per launch
 # (tests/test_ecdsa_p256_lane_gpu.py)

@@ -186,6 +186,8 @@ ABI = [
       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p]),
     ("cbft_ecdsa_kernel_ms", ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float)]),
     ("cbft_ecdsa_load_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, _u32p]),
+    ("cbft_ecdsa_load_signers_curve", ctypes.c_int,
+     [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32, _u32p]),
     ("cbft_ecdsa_signer_status", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     ("cbft_ecdsa_signer_public_keys", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     ("cbft_ecdsa_unload_signers", ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32]),
@@ -578,13 +580,16 @@ class Context:
         _check(self.lib.cbft_ecdsa_kernel_ms(self.handle, ctypes.byref(out)), "cbft_ecdsa_kernel_ms")
         return out.value
 
-    # ------------------------------------------------------------------ ECDSA secp256k1 signing (RFC 6979)
-    def ecdsa_load_signers(self, privs) -> int:
-        """privs: 32-byte big-endian private keys; returns the signer table id."""
+    # ------------------------------------------------------------------ ECDSA signing (RFC 6979)
+    def ecdsa_load_signers(self, privs, curve: str = "secp256k1") -> int:
+        """privs: 32-byte big-endian private keys; returns the signer table id.
+        curve: "secp256k1" or "p256"; the table remembers it and every other ecdsa_sign* / ecdsa_signer* call follows."""
+        if curve not in ECDSA_CURVES:
+            raise ValueError(f"unknown ECDSA curve {curve!r}")
         k = _as_rows(privs, 32)
         tid = ctypes.c_uint32()
-        _check(self.lib.cbft_ecdsa_load_signers(self.handle, _ptr(k), k.shape[0], ctypes.byref(tid)),
-               "cbft_ecdsa_load_signers")
+        _check(self.lib.cbft_ecdsa_load_signers_curve(self.handle, ECDSA_CURVES[curve], _ptr(k), k.shape[0],
+                                                       ctypes.byref(tid)), "cbft_ecdsa_load_signers_curve")
         return tid.value
 
     def ecdsa_signer_status(self, tid: int, nkeys: int) -> np.ndarray:

@@ -1,8 +1,10 @@
-// libcbft_hipcrypto, ECDSA secp256k1 signing half of the C ABI (include/cbft_hipcrypto.h).
+// libcbft_hipcrypto, ECDSA signing half of the C ABI (include/cbft_hipcrypto.h).
 //
-// The batch form of concord::util::crypto::ECDSASigner (util/src/crypto_utils.cpp:66-99): a signer
-// table is loaded once (range check and public key x G on the GPU) and every sign is a batch on the
-// GPU (ecdsa_sign.hip), with RFC 6979 nonces.
+// The batch form of concord::util::crypto::ECDSASigner (util/src/crypto_utils.cpp:66-99, secp256k1)
+// and of concord::util::openssl_utils::AsymmetricPrivateKey::sign (util/src/openssl_crypto.cpp,
+// P-256): a signer table is loaded once (range check and public key x G on the GPU) and every sign
+// is a batch on the GPU (ecdsa_sign.hip, ecdsa_p256_sign.hip), with RFC 6979 nonces.  A table
+// remembers its curve and every later call dispatches on it; each curve has its own comb table.
 //
 // Multi-GPU contexts: signer tables live on the lowest device (cbft_dev0) and the host-array calls
 // run there, like Ed25519 signing; the _device entry needs a single-GPU context.
@@ -19,6 +21,7 @@
 #include <vector>
 
 #include "cbft_internal.h"
+#include "ecdsa_p256_sign.h"
 #include "ecdsa_sign.h"
 
 static_assert(CBFT_ECDSA_PRIVATE_KEY_BYTES == ECDSAS_PRIV_BYTES, "key size");
@@ -29,7 +32,12 @@ static int ecdsas_launch_locked(cbft_ctx* c, EcdsaSignerTable& st, const uint32_
   CBFT_HIP(c->ecdsas.scratch.acquire(cbft_ecdsa_sign_scratch_words(n) * sizeof(uint32_t), s));
   EcdsaSignBatch b{n, st.rec.as<uint32_t>(), st.nkeys, d_idx, d_msg, d_off, d_len, fixed_len};
   CBFT_HIP(c->ecdsas.timer.begin(c->profiling, s));
-  CBFT_HIP(cbft_ecdsa_sign_launch(b, c->ecdsas.table.as<uint32_t>(), c->ecdsas.scratch.buf.as<uint32_t>(), d_sig, s));
+  if (st.curve == CBFT_CURVE_P256) {
+    CBFT_HIP(cbft_ecdsa_p256_sign_launch(b, c->ecdsas.table_p256.as<uint32_t>(), c->ecdsas.scratch.buf.as<uint32_t>(),
+                                         d_sig, s));
+  } else {
+    CBFT_HIP(cbft_ecdsa_sign_launch(b, c->ecdsas.table.as<uint32_t>(), c->ecdsas.scratch.buf.as<uint32_t>(), d_sig, s));
+  }
   CBFT_HIP(c->ecdsas.timer.end(c->profiling, s));
   CBFT_HIP(c->ecdsas.scratch.commit(s));
   return CBFT_OK;
@@ -41,7 +49,7 @@ void cbft_ecdsa_sign_release(cbft_ctx* c) {
   for (auto& kv : c->ecdsa_signer_tables) cbft_clear_release(kv.second.rec, c->stream);
   (void)hipStreamSynchronize(c->stream);
   c->ecdsa_signer_tables.clear();
-  for (DevBuf* b : {&c->ecdsas.table, &c->ecdsas.in, &c->ecdsas.out}) b->release();
+  for (DevBuf* b : {&c->ecdsas.table, &c->ecdsas.table_p256, &c->ecdsas.in, &c->ecdsas.out}) b->release();
   c->ecdsas.scratch.release();
   c->ecdsas.timer.release();
 }
@@ -54,23 +62,32 @@ static EcdsaSignerTable* ecdsas_find(cbft_ctx* c, uint32_t id) {
 extern "C" {
 
 int cbft_ecdsa_load_signers(cbft_ctx* c, const uint8_t* priv, uint32_t nkeys, uint32_t* out_id) {
+  return cbft_ecdsa_load_signers_curve(c, CBFT_CURVE_SECP256K1, priv, nkeys, out_id);
+}
+
+int cbft_ecdsa_load_signers_curve(cbft_ctx* c, int curve, const uint8_t* priv, uint32_t nkeys, uint32_t* out_id) {
   c = cbft_dev0(c);
   if (!c) return CBFT_EINVAL;
+  if (curve != CBFT_CURVE_SECP256K1 && curve != CBFT_CURVE_P256) return CBFT_EINVAL;
   if (nkeys > CBFT_ECDSA_MAX_KEYS) return CBFT_E2BIG;
   if (!priv || !out_id || nkeys == 0) return CBFT_EINVAL;
+  const bool p256 = curve == CBFT_CURVE_P256;
   std::lock_guard<std::mutex> g(c->mu);
   CBFT_HIP(hipSetDevice(c->device));
-  if (!c->ecdsas.table.p) {
-    CBFT_HIP(c->ecdsas.table.reserve((size_t)ECDSAS_TABLE_WORDS * sizeof(uint32_t)));
-    hipError_t e = cbft_ecdsa_sign_build_table(c->ecdsas.table.as<uint32_t>(), c->stream);
+  DevBuf& comb = p256 ? c->ecdsas.table_p256 : c->ecdsas.table;
+  if (!comb.p) {
+    CBFT_HIP(comb.reserve((size_t)ECDSAS_TABLE_WORDS * sizeof(uint32_t)));
+    hipError_t e = p256 ? cbft_ecdsa_p256_sign_build_table(comb.as<uint32_t>(), c->stream)
+                        : cbft_ecdsa_sign_build_table(comb.as<uint32_t>(), c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) {
-      c->ecdsas.table.release();
+      comb.release();
       return cbft_fail(e, "ecdsa sign comb table", __FILE__, __LINE__);
     }
   }
   EcdsaSignerTable st;
   st.nkeys = nkeys;
+  st.curve = curve;
   const size_t kbytes = (size_t)nkeys * ECDSAS_PRIV_BYTES;
   CBFT_HIP(st.rec.reserve((size_t)nkeys * ECDSAS_WORDS * sizeof(uint32_t)));
   HostBuf hs;
@@ -82,8 +99,10 @@ int cbft_ecdsa_load_signers(cbft_ctx* c, const uint8_t* priv, uint32_t nkeys, ui
     e = hipMemcpyAsync(ds.p, hs.p, kbytes, hipMemcpyHostToDevice, c->stream);
   }
   if (e == hipSuccess)
-    e = cbft_ecdsa_sign_launch_keys(ds.as<uint8_t>(), nkeys, c->ecdsas.table.as<uint32_t>(), st.rec.as<uint32_t>(),
-                                    c->stream);
+    e = p256 ? cbft_ecdsa_p256_sign_launch_keys(ds.as<uint8_t>(), nkeys, comb.as<uint32_t>(), st.rec.as<uint32_t>(),
+                                                c->stream)
+             : cbft_ecdsa_sign_launch_keys(ds.as<uint8_t>(), nkeys, comb.as<uint32_t>(), st.rec.as<uint32_t>(),
+                                           c->stream);
   const hipError_t e2 = hipStreamSynchronize(c->stream);
   if (e == hipSuccess) e = e2;
   if (hs.p) cbft_wipe(hs.p, hs.cap);  // the keys are on the device (or the load failed): none stay here

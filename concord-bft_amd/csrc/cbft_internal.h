@@ -263,10 +263,11 @@ struct BlsSignerTable {
   DevBuf rec, vk65;
 };
 
-// ECDSA secp256k1 signer table: per-signer records (x, public key Q = x G, validity) built on the
-// GPU at load time (ecdsa_sign.h ECDSAS_WORDS)
+// ECDSA signer table: per-signer records (x, public key Q = x G, validity) built on the GPU at load
+// time (ecdsa_sign.h ECDSAS_WORDS; the same layout on both curves)
 struct EcdsaSignerTable {
   uint32_t nkeys = 0;
+  int curve = 0;  // CBFT_CURVE_*: which lane code built the records and signs with them
   DevBuf rec;
 };
 
@@ -411,6 +412,7 @@ struct cbft_ctx {
   uint32_t next_ecdsa_signer_id = 1;
   struct {
     DevBuf table;       // comb of G (ecdsa_sign.h), built at the first load_signers; public
+    DevBuf table_p256;  // comb of P-256's G (ecdsa_p256_sign.h), built at that curve's first load_signers; public
     ScratchGuard scratch;  // the batch's nonces k (secret, zeroed by their reader, at unload and close), digests, states
     DevBuf in, out;     // packed inputs / signatures of a host-array batch
     KernelTimer timer;  // around the last signing batch's kernel

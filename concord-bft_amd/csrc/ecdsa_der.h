@@ -63,3 +63,55 @@ inline bool ecdsa_der_to_rs(const uint8_t* der, size_t len, size_t order_bytes, 
   if (!integer(der, len, &pos, order_bytes, out_rs + order_bytes)) return false;
   return pos == len;  // nothing after s inside the SEQUENCE
 }
+
+// The writer: r || s (each order_bytes wide, big-endian) -> the canonical SEQUENCE { INTEGER r,
+// INTEGER s } that ecdsa_der_to_rs accepts (what i2d_ECDSA_SIG writes): shortest lengths, and a
+// leading 00 only when the value's top bit is set (the value 0 is the single byte 00).
+// out: at least ECDSA_DER_MAX_BYTES(order_bytes) bytes; *out_len = bytes written.
+#define ECDSA_DER_MAX_BYTES(order_bytes) (2 * ((order_bytes) + 1 + 5) + 6)
+namespace ecdsa_der_detail {
+inline size_t put_length(uint8_t* out, size_t n) {
+  if (n < 0x80) {
+    out[0] = (uint8_t)n;
+    return 1;
+  }
+  size_t nb = 0;
+  for (size_t v = n; v; v >>= 8) nb++;
+  out[0] = (uint8_t)(0x80 | nb);
+  for (size_t i = 0; i < nb; i++) out[1 + i] = (uint8_t)(n >> (8 * (nb - 1 - i)));
+  return 1 + nb;
+}
+// the INTEGER's content length: the value without leading zero bytes (one byte at least), plus the sign byte
+inline size_t integer_bytes(const uint8_t* v, size_t width, size_t* skip) {
+  size_t z = 0;
+  while (z + 1 < width && v[z] == 0) z++;
+  *skip = z;
+  return (width - z) + ((v[z] & 0x80) ? 1 : 0);
+}
+inline size_t put_integer(uint8_t* out, const uint8_t* v, size_t width) {
+  size_t skip;
+  const size_t n = integer_bytes(v, width, &skip);
+  size_t pos = 0;
+  out[pos++] = 0x02;
+  pos += put_length(out + pos, n);
+  if (v[skip] & 0x80) out[pos++] = 0x00;
+  for (size_t i = skip; i < width; i++) out[pos++] = v[i];
+  return pos;
+}
+}  // namespace ecdsa_der_detail
+
+inline bool ecdsa_rs_to_der(const uint8_t* rs, size_t order_bytes, uint8_t* out, size_t* out_len) {
+  using namespace ecdsa_der_detail;
+  if (!rs || !out || !out_len || order_bytes == 0) return false;
+  uint8_t lenbuf[1 + sizeof(size_t)];
+  size_t skip;
+  const size_t nr = integer_bytes(rs, order_bytes, &skip), ns = integer_bytes(rs + order_bytes, order_bytes, &skip);
+  const size_t body = (1 + put_length(lenbuf, nr) + nr) + (1 + put_length(lenbuf, ns) + ns);
+  size_t pos = 0;
+  out[pos++] = 0x30;
+  pos += put_length(out + pos, body);
+  pos += put_integer(out + pos, rs, order_bytes);
+  pos += put_integer(out + pos, rs + order_bytes, order_bytes);
+  *out_len = pos;
+  return true;
+}

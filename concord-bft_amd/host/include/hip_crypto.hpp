@@ -16,6 +16,8 @@
 //                                  keys on other curves on the host OpenSSL
 //   HipP256PublicKey               ECDSA P-256 / SHA-256 with DER signatures, the shape of
 //                                  concord::util::openssl_utils::AsymmetricPublicKey (openssl_crypto.cpp)
+//   HipP256PrivateKey              its private half (AsymmetricPrivateKey): RFC 6979 signatures in DER, sign() with
+//                                  the GPU's lane code on the host, signBatch() on the GPU
 //   EdDSASigner : ISigner          Ed25519 signing: sign() on the host OpenSSL (one signature is
 //                                  latency-bound on any device); signBatch() on the GPU from
 //                                  CBFT_SIGN_GPU_MIN requests up (the pre-processing path signs one
@@ -230,6 +232,51 @@ class HipP256PublicKey {
   std::unique_ptr<HipECDSAVerifier> verifier_;
 };
 
+// Smallest HipP256PrivateKey::signBatch that goes to the GPU ($CBFT_ECDSA_P256_SIGN_GPU_MIN overrides): the
+// crossover of one cbft_ecdsa_sign_batch call on a P-256 signer table, host arrays in to host arrays out,
+// against the class's own host loop on one core, rounded up to a power of two
+// (profiles/ecdsa_p256_sign.json "crossover").
+#define CBFT_ECDSA_P256_SIGN_GPU_MIN_DEFAULT 16
+
+// ECDSA P-256 / SHA-256 private key in the shape of concord::util::openssl_utils::AsymmetricPrivateKey
+// (util/include/openssl_crypto.hpp), the counterpart of HipP256PublicKey: built from the serialised form
+// "PRIVATE_KEY:secp256r1:<hex scalar>", signs to DER.  The reference signs with EVP_DigestSign and a random
+// nonce; here the nonce is RFC 6979's, so a signature is reproducible: sign() runs the GPU's
+// lane code (csrc/ecdsa_p256_sign.h) built for the host, signBatch() the GPU from gpuMinBatchP256Sign()
+// requests up, byte for byte the same; csrc/ecdsa_der.h writes the DER form.
+class HipP256PrivateKey {
+ public:
+  // Throws std::invalid_argument unless `serialized` is PRIVATE_KEY:secp256r1: and a hex scalar in [1, n - 1].
+  explicit HipP256PrivateKey(const std::string& serialized);
+  ~HipP256PrivateKey();  // unloads the key from the GPU and wipes the scalar
+  HipP256PrivateKey(const HipP256PrivateKey&) = delete;
+  HipP256PrivateKey& operator=(const HipP256PrivateKey&) = delete;
+
+  std::string sign(const std::string& message) const;  // DER SEQUENCE { INTEGER r, INTEGER s }
+  std::string serialize() const;                       // PRIVATE_KEY:secp256r1:<scalar>, upper-case hex as BN_bn2hex
+  std::string publicKeySerialized() const;             // PUBLIC_KEY:secp256r1:04<X><Y>, as HipP256PublicKey takes it
+
+  struct Request {
+    const HipP256PrivateKey* key;
+    const char* data;
+    size_t dataLength;
+    std::string* outSig;  // receives the DER signature
+  };
+  // *reqs[i].outSig = reqs[i].key->sign(reqs[i].data) for every request.  gpuMinBatchP256Sign() requests or more:
+  // one cbft_ecdsa_sign_batch call per distinct key on the process's ECDSA engine (a key is loaded into it at
+  // its first such batch); below that count, or for a key whose GPU call fails (counted in
+  // ecdsaP256SignStats().gpu_errors), the host loop over sign().  A request with a null key or outSig is skipped.
+  static void signBatch(std::vector<Request>& reqs);
+  static size_t gpuMinBatchP256Sign();
+
+ private:
+  void signRaw(const char* data, size_t len, uint8_t rs[64]) const;
+  uint8_t scalar_[32];  // big-endian; wiped by the destructor
+  uint8_t pub_[64];     // X || Y
+  mutable std::shared_ptr<EcdsaEngine> engine_;  // set once the key is loaded for signBatch
+  mutable uint32_t signer_table_ = 0;
+};
+
 // Smallest secp256k1 HipECDSASigner::signBatch that goes to the GPU ($CBFT_ECDSA_SIGN_GPU_MIN
 // overrides): the measured crossover of one cbft_ecdsa_sign_batch call, host arrays in to host
 // arrays out, against a loop of sign() (the lane code built for the host) on one core, rounded up to
@@ -373,6 +420,7 @@ struct SignStats {
 SignStats ed25519SignStats();
 SignStats rsaSignStats();  // the same for HipRSASigner::signBatch
 SignStats ecdsaSignStats();  // the same for HipECDSASigner::signBatch
+SignStats ecdsaP256SignStats();  // the same for HipP256PrivateKey::signBatch; a GPU batch is one call for one key
 // prime256v1 verification in HipECDSAVerifier::verifyBatch: GPU batches and their items, items verified on
 // the host below gpuMinBatchP256(), failed GPU calls (their items come out false)
 struct EcdsaP256VerifyStats {

@@ -14,6 +14,11 @@
 // EC private key.  secp256k1 keys sign with RFC 6979 nonces: sign() with the lane code of
 // csrc/ecdsa_sign.h built for the host, signBatch() on the GPU from gpuMinBatch() requests up, byte
 // for byte the same; other curves sign with the host OpenSSL.
+//
+// HipP256PrivateKey is the shape of concord::util::openssl_utils::AsymmetricPrivateKey (util/src/
+// openssl_crypto.cpp, EVPPKEYPrivateKey) over a secp256r1 scalar: RFC 6979 signatures in DER, sign() with the
+// lane code of csrc/ecdsa_p256_sign.h built for the host, signBatch() on the GPU from gpuMinBatchP256Sign()
+// requests up, byte for byte the same.
 #include <openssl/bio.h>
 #include <openssl/bn.h>
 #include <openssl/core_names.h>
@@ -31,8 +36,9 @@
 
 #include <openssl/crypto.h>
 
-#include "../../csrc/ecdsa_der.h"   // DER -> r || s for HipP256PublicKey
-#include "../../csrc/ecdsa_sign.h"  // the signing lane code, host build
+#include "../../csrc/ecdsa_der.h"        // DER -> r || s for HipP256PublicKey, r || s -> DER for HipP256PrivateKey
+#include "../../csrc/ecdsa_p256_sign.h"  // the P-256 signing lane code, host build
+#include "../../csrc/ecdsa_sign.h"       // the signing lane code, host build
 #include "cbft_hipcrypto.h"
 #include "hip_crypto.hpp"
 
@@ -82,6 +88,19 @@ const uint32_t* hostCombTable() {
 }
 
 std::atomic<uint64_t> g_p256_gpu_batches{0}, g_p256_gpu_items{0}, g_p256_host_items{0}, g_p256_gpu_errors{0};
+// the same for P-256 (csrc/ecdsa_p256_sign.h)
+const uint32_t* hostCombTableP256() {
+  static std::once_flag once;
+  static std::vector<uint32_t> tbl;
+  std::call_once(once, [] {
+    tbl.assign(ECDSAS_TABLE_WORDS, 0);
+    for (int j = 0; j < ECDSAS_TABLE_LANES; j++) p2s_table_lane(tbl.data(), j);
+  });
+  return tbl.data();
+}
+
+std::atomic<uint64_t> g_p256_sign_gpu_batches{0}, g_p256_sign_gpu_items{0}, g_p256_sign_host_items{0},
+    g_p256_sign_gpu_errors{0};
 std::atomic<uint64_t> g_sign_gpu_batches{0}, g_sign_gpu_items{0}, g_sign_host_items{0}, g_sign_gpu_errors{0};
 std::mutex g_sign_register_mu;
 
@@ -129,6 +148,11 @@ class EcdsaEngine {
   int loadSigner(const uint8_t priv[32], uint32_t* id) {
     open();
     return cbft_ecdsa_load_signers(ctx_, priv, 1, id);
+  }
+  // the same on a named curve (HipP256PrivateKey::signBatch)
+  int loadSignerCurve(int curve, const uint8_t priv[32], uint32_t* id) {
+    open();
+    return cbft_ecdsa_load_signers_curve(ctx_, curve, priv, 1, id);
   }
   void unloadSigner(uint32_t id) { (void)cbft_ecdsa_unload_signers(ctx_, id); }
   int signBatch(uint32_t id, const uint8_t* blob, const uint64_t* off, const uint32_t* len, size_t n, uint8_t* sig) {
@@ -434,6 +458,185 @@ void HipP256PublicKey::verifyBatch(const std::vector<Request>& reqs, std::vector
   std::vector<bool> got;
   HipECDSAVerifier::verifyBatch(vr, got);
   for (size_t j = 0; j < pos.size(); j++) out[pos[j]] = got[j];
+}
+
+// ---- HipP256PrivateKey ---------------------------------------------------------------------------
+namespace {
+const char kP256PrivPrefix[] = "PRIVATE_KEY:secp256r1:";
+const char kHexUpper[] = "0123456789ABCDEF";
+}  // namespace
+
+HipP256PrivateKey::HipP256PrivateKey(const std::string& serialized) {
+  std::memset(scalar_, 0, sizeof scalar_);
+  std::memset(pub_, 0, sizeof pub_);
+  const size_t a = serialized.find(':'), b = a == std::string::npos ? a : serialized.find(':', a + 1);
+  if (b == std::string::npos || serialized.compare(0, a, "PRIVATE_KEY") != 0)
+    throw std::invalid_argument("HipP256PrivateKey: input is not labeled as a private key");
+  if (serialized.compare(a + 1, b - a - 1, "secp256r1") != 0)
+    throw std::invalid_argument("HipP256PrivateKey: scheme is not secp256r1");
+  // the scalar as BN_hex2bn reads it: hex digits of either case, any number of leading zeros
+  size_t i = b + 1;
+  const size_t end = serialized.size();
+  bool ok = i < end;
+  while (i < end && serialized[i] == '0') i++;
+  ok = ok && end - i <= 64;
+  uint8_t nib[64] = {0};
+  for (size_t j = i; ok && j < end; j++) {
+    const char c = serialized[j];
+    const int v = c >= '0' && c <= '9' ? c - '0' : c >= 'a' && c <= 'f' ? c - 'a' + 10 : c >= 'A' && c <= 'F' ? c - 'A' + 10 : -1;
+    ok = v >= 0;
+    if (ok) nib[64 - (end - j)] = (uint8_t)v;
+  }
+  if (!ok) {
+    OPENSSL_cleanse(nib, sizeof nib);
+    throw std::invalid_argument("HipP256PrivateKey: key data is not a hexadecimal scalar of at most 256 bits");
+  }
+  for (int j = 0; j < 32; j++) scalar_[j] = (uint8_t)((nib[2 * j] << 4) | nib[2 * j + 1]);
+  OPENSSL_cleanse(nib, sizeof nib);
+  // range check and public key by the lane code: 0 or >= n gives a record with its validity clear
+  uint32_t rec[ECDSAS_WORDS];
+  p2s_signer_lane(rec, scalar_, hostCombTableP256());
+  const bool usable = rec[ECDSAS_OK] != 0;
+  k1_to_be(pub_, rec + 8);
+  k1_to_be(pub_ + 32, rec + 16);
+  OPENSSL_cleanse(rec, sizeof rec);
+  if (!usable) {
+    OPENSSL_cleanse(scalar_, sizeof scalar_);
+    throw std::invalid_argument("HipP256PrivateKey: the scalar is 0 or not below the group order");
+  }
+}
+
+HipP256PrivateKey::~HipP256PrivateKey() {
+  if (engine_) engine_->unloadSigner(signer_table_);
+  OPENSSL_cleanse(scalar_, sizeof scalar_);
+}
+
+size_t HipP256PrivateKey::gpuMinBatchP256Sign() {
+  static const size_t v = [] {
+    const char* e = std::getenv("CBFT_ECDSA_P256_SIGN_GPU_MIN");
+    const long long x = e ? std::atoll(e) : 0;
+    return x > 0 ? (size_t)x : (size_t)CBFT_ECDSA_P256_SIGN_GPU_MIN_DEFAULT;
+  }();
+  return v;
+}
+
+std::string HipP256PrivateKey::serialize() const {
+  std::string out = kP256PrivPrefix;
+  int i = 0;
+  while (i < 31 && scalar_[i] == 0) i++;  // BN_bn2hex: whole bytes, no leading zero byte
+  for (; i < 32; i++) {
+    out += kHexUpper[scalar_[i] >> 4];
+    out += kHexUpper[scalar_[i] & 15];
+  }
+  return out;
+}
+
+std::string HipP256PrivateKey::publicKeySerialized() const {
+  std::string out = kP256Prefix;
+  out += "04";
+  for (int i = 0; i < 64; i++) {
+    out += kHexUpper[pub_[i] >> 4];
+    out += kHexUpper[pub_[i] & 15];
+  }
+  return out;
+}
+
+// r || s by the lane code of the GPU kernels, built for the host: the same bytes, the same construction
+void HipP256PrivateKey::signRaw(const char* data, size_t len, uint8_t rs[64]) const {
+  if (len > 0xFFFFFFFFull) throw std::runtime_error("HipP256PrivateKey: message too long");
+  uint32_t x[8], h1[8], sig[16];
+  k1_from_be(x, scalar_);
+  ecdsa_sha256(h1, reinterpret_cast<const uint8_t*>(data), (uint32_t)len);
+  p2s_sign_lane(sig, x, h1, hostCombTableP256());
+  std::memcpy(rs, sig, 64);
+  OPENSSL_cleanse(x, sizeof x);
+}
+
+namespace {
+std::string derOf(const uint8_t rs[64]) {
+  uint8_t der[ECDSA_DER_MAX_BYTES(32)];
+  size_t n = 0;
+  if (!ecdsa_rs_to_der(rs, 32, der, &n)) throw std::runtime_error("HipP256PrivateKey: DER encoding failed");
+  return std::string(reinterpret_cast<const char*>(der), n);
+}
+}  // namespace
+
+std::string HipP256PrivateKey::sign(const std::string& message) const {
+  uint8_t rs[64];
+  signRaw(message.data(), message.size(), rs);
+  return derOf(rs);
+}
+
+void HipP256PrivateKey::signBatch(std::vector<Request>& reqs) {
+  std::vector<size_t> live;
+  for (size_t i = 0; i < reqs.size(); i++)
+    if (reqs[i].key && reqs[i].outSig) live.push_back(i);
+  if (live.empty()) return;
+  std::vector<bool> done(reqs.size(), false);
+  if (live.size() >= gpuMinBatchP256Sign()) {
+    std::map<const HipP256PrivateKey*, std::vector<size_t>> byKey;  // one signer table, one call, per key
+    for (size_t i : live) byKey[reqs[i].key].push_back(i);
+    for (auto& kv : byKey) {
+      const HipP256PrivateKey* key = kv.first;
+      const std::vector<size_t>& ps = kv.second;
+      const size_t n = ps.size();
+      try {
+        {
+          std::lock_guard<std::mutex> g(g_sign_register_mu);
+          if (!key->engine_) {
+            auto engine = EcdsaEngine::get();
+            uint32_t id = 0;
+            const int rc = engine->loadSignerCurve(CBFT_CURVE_P256, key->scalar_, &id);  // throws when the engine cannot be opened
+            if (rc != CBFT_OK) throw std::runtime_error("cbft_ecdsa_load_signers_curve");
+            key->engine_ = std::move(engine);
+            key->signer_table_ = id;
+          }
+        }
+        size_t blob = 0;
+        bool fits = true;
+        for (size_t i : ps) {
+          fits = fits && reqs[i].dataLength <= 0xFFFFFF00u;
+          blob += reqs[i].dataLength;
+        }
+        if (!fits) throw std::runtime_error("message too long for the GPU signer");
+        std::vector<uint8_t> msg(blob ? blob : 1), sig(n * 64);
+        std::vector<uint64_t> off(n);
+        std::vector<uint32_t> len(n);
+        size_t o = 0;
+        for (size_t j = 0; j < n; j++) {
+          const Request& r = reqs[ps[j]];
+          off[j] = o;
+          len[j] = (uint32_t)r.dataLength;
+          if (r.dataLength) std::memcpy(&msg[o], r.data, r.dataLength);
+          o += r.dataLength;
+        }
+        const int rc = key->engine_->signBatch(key->signer_table_, msg.data(), off.data(), len.data(), n, sig.data());
+        if (rc != CBFT_OK) throw std::runtime_error("cbft_ecdsa_sign_batch");
+        for (size_t j = 0; j < n; j++) {
+          *reqs[ps[j]].outSig = derOf(&sig[64 * j]);
+          done[ps[j]] = true;
+        }
+        g_p256_sign_gpu_batches++;
+        g_p256_sign_gpu_items += n;
+      } catch (...) {
+        g_p256_sign_gpu_errors++;
+      }
+    }
+  }
+  uint64_t host = 0;
+  for (size_t i : live) {
+    if (done[i]) continue;
+    uint8_t rs[64];
+    reqs[i].key->signRaw(reqs[i].data, reqs[i].dataLength, rs);
+    *reqs[i].outSig = derOf(rs);
+    host++;
+  }
+  g_p256_sign_host_items += host;
+}
+
+SignStats ecdsaP256SignStats() {
+  return SignStats{g_p256_sign_gpu_batches.load(), g_p256_sign_gpu_items.load(), g_p256_sign_host_items.load(),
+                   g_p256_sign_gpu_errors.load()};
 }
 
 // ---- HipECDSASigner ------------------------------------------------------------------------------

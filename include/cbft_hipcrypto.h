@@ -668,6 +668,17 @@ int cbft_ecdsa_kernel_ms(cbft_ctx* ctx, float* out_ms);
  * and at cbft_close.
  * Multi-GPU contexts keep signer tables on their first device. */
 int cbft_ecdsa_load_signers(cbft_ctx* ctx, const uint8_t* priv, uint32_t nkeys, uint32_t* out_signer_table_id);
+/* The same for a named curve (CBFT_CURVE_SECP256K1, CBFT_CURVE_P256).  CBFT_CURVE_P256 is NIST P-256
+ * (secp256r1, prime256v1) with SHA-256: the batch form of concord::util::openssl_utils::
+ * AsymmetricPrivateKey::sign (util/src/openssl_crypto.cpp) with the signature as r || s here
+ * (csrc/ecdsa_der.h's ecdsa_rs_to_der writes the DER form on the host).  The scheme is the one above with
+ * P-256's n and G (tests/p256_sign_ref.py restates it, tests/golden/ecdsa_p256_sign_vectors.json pins it,
+ * RFC 6979 A.2.5 included); OpenSSL's ECDSA_do_verify on prime256v1 and cbft_ecdsa_verify_batch on a
+ * P-256 key table accept the signatures.  A signer table remembers its curve and
+ * every other cbft_ecdsa_*sign* / *signer* call dispatches on it; signer table ids of both curves share
+ * one space; cbft_ecdsa_load_signers is curve 0.  An unknown curve is CBFT_EINVAL. */
+int cbft_ecdsa_load_signers_curve(cbft_ctx* ctx, int curve, const uint8_t* priv, uint32_t nkeys,
+                                  uint32_t* out_signer_table_id);
 /* out_ok: nkeys bytes, 1 = the key is usable */
 int cbft_ecdsa_signer_status(cbft_ctx* ctx, uint32_t signer_table_id, uint8_t* out_ok);
 /* out_pub: nkeys x 64 bytes, X || Y big-endian as cbft_ecdsa_load_keys takes them; 64 zero bytes for
